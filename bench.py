@@ -12,7 +12,12 @@ Multi-GPU: one process per GPU (torch.distributed.run); every rank searches its 
 (weak scaling, no data-path collective); the verdict bitmaps are all-gathered once after the
 timed region (RCCL), which is the only collective the path has.
 
-Prints one JSON line (rank 0) with roofline (integer VALU) and cpu_baseline objects.
+A plain run sets up, warms up, times the ``--steps`` steps and prints one JSON line (rank 0)
+with the headline figure, ``ms_per_step`` and the timed kernel's integer-VALU roofline.
+``--dump-outputs DIR`` also writes what the last timed step returned (dump_outputs).
+``--full`` adds every other leg to the line — the early-exit search, Keccak (config 4), the
+1,000,000-DAG full pass, the query corpus (discharge), quick-sat and the CPU baselines —
+each with its own option below; without ``--full`` none of them runs.
 """
 
 from __future__ import annotations
@@ -59,7 +64,53 @@ def parse(argv=None):
     ap.add_argument("--full-pass-workers", type=int, default=16)
     ap.add_argument("--quick-sat-queries", type=int, default=120,
                     help="queries of the quick-sat (100 cached models) and funnel legs (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: early exit, Keccak, full pass, "
+                         "corpus discharge, quick-sat, CPU baselines, the SURVEY op-table roofline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
+
+
+# --dump-outputs: at most this many verdicts are written (float64: 32 MB of the 64 MB allowed)
+DUMP_MAX_VERDICTS = 1 << 22
+
+
+def dump_outputs(path, result):
+    """What a caller of the timed path receives from its last step (engine.CheckResult), as
+    float64 arrays: ``found.npy`` — per set the index of the witness candidate, 0xFFFFFFFF
+    where none of the candidates satisfies the set (a fixed seeded sample of the sets, in set
+    order, beyond DUMP_MAX_VERDICTS); ``counters.npy`` — evals_full, cands_decided, ops.  The
+    inputs are functions of the arguments alone (DAG ids, candidate seed), so two builds run
+    with the same arguments are comparable array for array."""
+    os.makedirs(path, exist_ok=True)
+    found = np.asarray(result.found)
+    if found.size > DUMP_MAX_VERDICTS:
+        keep = np.random.default_rng(0x44554D50).choice(found.size, DUMP_MAX_VERDICTS, replace=False)
+        found = found[np.sort(keep)]
+    np.save(os.path.join(path, "found.npy"), found.astype(np.float64))
+    np.save(os.path.join(path, "counters.npy"),
+            np.array([result.evals_full, result.cands_decided, result.ops], dtype=np.float64))
+
+
+def step_programs(firsts, sets):
+    """The config-3 programs of every step (DAG ids first .. first + sets - 1 per step), in
+    step order.  The first step is generated on this thread (it loads and binds the native
+    generator), the others on a few threads: the generator is a function of the DAG id alone
+    and runs outside the interpreter lock, so set-up does not grow with the step count at
+    one core's pace."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from mythril_amd import synth
+
+    def gen(first):
+        return synth.random_dag_programs(first, sets, plant=False)[0]
+
+    out = [gen(f) for f in firsts[:1]]
+    if len(firsts) > 1:
+        with ThreadPoolExecutor(min(8, len(firsts) - 1)) as ex:
+            out += list(ex.map(gen, firsts[1:]))
+    return out
 
 
 def cpu_baseline(programs, budget, seed, target_s):
@@ -479,7 +530,7 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
     (tests/test_bench_dist.py), not first in the driver's SCALE run."""
     import torch
 
-    from mythril_amd import _lib, ir, synth
+    from mythril_amd import _lib, ir
     from mythril_amd.engine import Engine
 
     if args.lib:
@@ -488,13 +539,9 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
     eng = engine if engine is not None else Engine(local)
     flags = ir.FLAG_COUNT_OPS | (ir.FLAG_EARLY_EXIT | ir.FLAG_SHORTCIRCUIT if args.mode == "early" else 0)
     n_steps = args.warmup + args.steps
-    batches, step_progs = [], []
     t_gen = time.perf_counter()
-    for k in range(n_steps):
-        first = (k * world + rank) * args.sets
-        progs = synth.random_dag_programs(first, args.sets, plant=False)[0]
-        step_progs.append(progs)
-        batches.append(eng.upload(progs))
+    step_progs = step_programs([(k * world + rank) * args.sets for k in range(n_steps)], args.sets)
+    batches = [eng.upload(progs) for progs in step_progs]
     t_gen = time.perf_counter() - t_gen
 
     def barrier():
@@ -527,6 +574,8 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
         founds.append(r.found)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and results:
+        dump_outputs(args.dump_outputs, results[-1])
 
     tot_evals, max_dt = float(evals), dt
     if dist is not None:
@@ -552,14 +601,14 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
         tot_nodes = float(x.item())
 
     early = (early_leg(args, eng, batches[args.warmup], torch, dist, (args.warmup * world + rank) * args.sets,
-                       cdev) if args.mode == "full" else None)
-    kec = keccak_leg(args, torch, rank, world) if args.keccak_log2 > 0 else None
+                       cdev) if args.full and args.mode == "full" else None)
+    kec = keccak_leg(args, torch, rank, world) if args.full and args.keccak_log2 > 0 else None
 
     # the SURVEY.md §8(d) op table's figure (prices EXP as 512 products and division as an
     # 8-digit schoolbook quotient, so its "achieved" can exceed the peak): kept as its own
     # field, computed on the host for the full sweep (every candidate runs every node)
     s8d = None
-    if args.mode == "full":
+    if args.full and args.mode == "full":
         s8d_ops = float(sum(ir.op_cost_words(batches[k].batch.code) for k in range(args.warmup, n_steps))) * args.budget
         ks = sum(kms) / 1e3
         s8d = {"achieved": s8d_ops / ks / 1e12 if ks > 0 else 0.0,
@@ -568,7 +617,7 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
                        "not reachable-work pricing, so frac may exceed 1"}
 
     # the full pass on every rank (its own shard of the DAG ids), before rank 0's host legs
-    fp = full_pass_leg(args, eng, rank, world, dist, cdev) if args.full_pass_dags > 0 else None
+    fp = full_pass_leg(args, eng, rank, world, dist, cdev) if args.full and args.full_pass_dags > 0 else None
 
     if rank == 0:
         pmc, traffic_src = pmc_traffic(args)
@@ -605,7 +654,7 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
             "early_exit": early,
             "gen_upload_s": t_gen,
         }
-        if args.keccak_log2 > 0:
+        if kec is not None:
             line["keccak"] = kec
             if pmc and "keccak" in pmc and args.keccak_log2 == 24:
                 kec["roofline"]["traffic"] = pmc["keccak"]["traffic_bytes"]
@@ -615,13 +664,13 @@ def run(args, rank, world, local, dist, engine=None, cdev="cuda"):
                 import coracle_py
 
                 line["keccak"]["cpu_baseline"] = coracle_py.keccak_baseline(64, 5.0)
-        if args.corpus_scenarios > 0:
+        if args.full and args.corpus_scenarios > 0:
             line["discharge"] = discharge(args)
-        if args.quick_sat_queries > 0:
+        if args.full and args.quick_sat_queries > 0:
             line["quick_sat"] = quick_sat_leg(args)
         if fp is not None:
             line["full_pass"] = fp
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(step_progs[args.warmup], args.budget, args.seed,
                                                 args.cpu_sample_s)
         if dist is not None:

@@ -14,7 +14,7 @@ import numpy as np
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGV = ["--sets", "3", "--budget", "64", "--steps", "2", "--warmup", "1", "--keccak-log2", "0", "--quick-sat-queries", "0", "--full-pass-dags", "0",
+ARGV = ["--full", "--sets", "3", "--budget", "64", "--steps", "2", "--warmup", "1", "--keccak-log2", "0", "--quick-sat-queries", "0", "--full-pass-dags", "0",
         "--corpus-scenarios", "0", "--no-cpu-baseline", "--seed", "5"]
 
 
@@ -90,6 +90,44 @@ def test_bench_multirank_branch_gloo(tmp_path):
     assert line["sets_with_witness"] == want
     ee = line["early_exit"]
     assert ee["unplanted"]["sets"] == 2 * a.sets and ee["planted"]["sets_with_witness"] == 2 * a.sets
+
+
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """Without --full the line carries the headline figures only — no early-exit, Keccak,
+    full-pass, corpus, quick-sat or CPU-baseline leg even with their options at the defaults —
+    and --dump-outputs writes the last timed step's verdicts and counters as float64 arrays,
+    the same from run to run."""
+    import bench
+    import pyoracle as O
+
+    from mythril_amd import ir, synth
+    from mythril_amd.engine import NOT_FOUND
+
+    argv = ["--sets", "3", "--budget", "64", "--steps", "2", "--warmup", "1", "--seed", "5"]
+    lines = []
+    for d in ("a", "b"):
+        a = bench.parse(argv + ["--dump-outputs", str(tmp_path / d)])
+        eng = _engine()
+        lines.append(bench.run(a, 0, 1, 0, None, engine=eng, cdev="cpu"))
+        assert eng.launches == a.warmup + a.steps
+    line = lines[0]
+    assert line["steps"] == a.steps and line["early_exit"] is None and line["roofline"]["s8d_table"] is None
+    assert not {"keccak", "discharge", "quick_sat", "full_pass", "cpu_baseline"} & set(line)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    tot = a.steps * a.sets * a.budget
+    assert abs(line["value"] - tot / (line["ms_per_step"] * a.steps / 1e3)) <= 1e-9 * line["value"]
+    found = np.load(tmp_path / "a" / "found.npy")
+    counters = np.load(tmp_path / "a" / "counters.npy")
+    assert found.dtype == np.float64 and counters.dtype == np.float64
+    last = (a.warmup + a.steps - 1) * a.sets
+    b = ir.Batch([synth.random_dag_set(last + i, plant=False)[0] for i in range(a.sets)])
+    want = [O.SetView.from_batch(b, i).check(a.budget, a.seed)[0] for i in range(a.sets)]
+    assert found.tolist() == [float(NOT_FOUND if w is None else w) for w in want]
+    assert counters.tolist() == [a.sets * a.budget, a.sets * a.budget, 0.0]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["counters.npy", "found.npy"]
+    for name in ("found.npy", "counters.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
 
 
 def _worker_fp(rank, world, port, out_path):

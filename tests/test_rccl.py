@@ -17,7 +17,7 @@ import socket
 import numpy as np
 import pytest
 
-ARGV = ["--sets", "64", "--budget", "4096", "--steps", "2", "--warmup", "1", "--keccak-log2", "12",
+ARGV = ["--full", "--sets", "64", "--budget", "4096", "--steps", "2", "--warmup", "1", "--keccak-log2", "12",
         "--quick-sat-queries", "0", "--full-pass-dags", "0", "--corpus-scenarios", "0", "--no-cpu-baseline",
         "--seed", "3"]
 

@@ -17,7 +17,7 @@ for W in ${EARLY_WPC:--}; do
     export PF_WAVES_PER_CU_EARLY=${W%%:*}
     case "$W" in *:*) export PF_EARLY_CHUNK_GROUPS=${W##*:};; esac
   fi
-  timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --corpus-scenarios ${CORPUS:-0} --keccak-log2 0 --lib $L > $O/b$i.log 2>&1 || { echo "BENCH $L $W FAILED"; tail -5 $O/b$i.log; exit 1; }
+  timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --corpus-scenarios ${CORPUS:-0} --keccak-log2 0 --lib $L > $O/b$i.log 2>&1 || { echo "BENCH $L $W FAILED"; tail -5 $O/b$i.log; exit 1; }
   python -c "import json; d=json.loads(open('$O/b$i.log').read().strip().splitlines()[-1]); e=d['early_exit']; q=d.get('discharge') or {}; print('$L', 'wpc=$W', round(d['value']/1e9,4), 'Gevals/s', 'unplanted', round(e['unplanted']['kernel_ms'],3), 'ms', e['unplanted']['sets_with_witness'], 'planted', round(e['planted']['kernel_ms'],3), 'ms', round(e['planted']['set_verdicts_per_s']), '/s', 'sq', (q.get('single_query_ms') or {}).get('median'))"
 done
 done

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 TAG=${1:-qs}; shift
 O=gpurun_out/$TAG
 mkdir -p $O
-B="python -u bench.py --steps 1 --warmup 0 --sets 64 --budget 64 --keccak-log2 0 --full-pass-dags 0 --corpus-scenarios 0 --no-cpu-baseline --quick-sat-queries ${QSQ:-121}"
+B="python -u bench.py --full --steps 1 --warmup 0 --sets 64 --budget 64 --keccak-log2 0 --full-pass-dags 0 --corpus-scenarios 0 --no-cpu-baseline --quick-sat-queries ${QSQ:-121}"
 i=0
 for v in "$@"; do
   i=$((i+1))

@@ -14,10 +14,10 @@ if [ -z "$NOTESTS" ]; then
   tail -1 $O/smoke.log
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1 || { echo "BENCH FAILED"; tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1 || { echo "BENCH FAILED"; tail -20 $O/bench.log; exit 1; }
   tail -1 $O/bench.log | cut -c1-400
 fi
-B="python -u bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --corpus-scenarios 0 --keccak-log2 0"
+B="python -u bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --corpus-scenarios 0 --keccak-log2 0"
 i=0
 for rep in 1 2; do
 for v in base "$@"; do

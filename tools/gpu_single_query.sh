@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 TAG=${1:-sq}; shift
 O=gpurun_out/$TAG
 mkdir -p $O
-B="python -u bench.py --steps 1 --warmup 0 --sets 64 --budget 64 --keccak-log2 0 --full-pass-dags 0 --quick-sat-queries 0 --no-cpu-baseline"
+B="python -u bench.py --full --steps 1 --warmup 0 --sets 64 --budget 64 --keccak-log2 0 --full-pass-dags 0 --quick-sat-queries 0 --no-cpu-baseline"
 i=0
 for rep in 1 2; do
 for v in "$@"; do

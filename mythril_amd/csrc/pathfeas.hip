@@ -288,9 +288,6 @@ int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uin
     Dev* D = find_dev(B->device);
     unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
     uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
-#ifndef PF_FULL_QUEUE
-#define PF_FULL_QUEUE 1
-#endif
     // t0 and the profiling slots at the front, the work-queue heads of both launch parts from
     // PF_EARLY_QUEUE_OFF, the counter lines from PF_COUNTER_OFF: one fill for all
     {
@@ -319,11 +316,9 @@ int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uin
         geometry(D->num_cus, (uint32_t)n, pbudget - cbegin, flags, &per_wave, &slices);
         const uint64_t items = (uint64_t)n * slices;
         if (items > 0xffffffffull) return fail("batch too large: %llu waves", (unsigned long long)items);
-        // early exit: a chip-filling grid of persistent waves takes the items from the queue
-        // heads (zeroed above); full sweep: one wave per item
-        const uint64_t waves = early ? std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early)
-                             : PF_FULL_QUEUE ? std::min<uint64_t>(items, (uint64_t)D->num_cus * 16u)
-                                             : items;
+        // a chip-filling grid of persistent waves takes the items from the queue heads
+        // (zeroed above), in the full sweep as in the early-exit search
+        const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * (early ? g_waves_per_cu_early : 16u));
         // each (phase, part) launch has its own heads, all zeroed by the reset above
         uint32_t* d_queue =
             B->d_scratch + PF_EARLY_QUEUE_OFF / 4 + (phase * 2 + part) * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;
@@ -499,7 +494,6 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
                 }
             }
         }
-#ifndef PF_NO_MOV_FUSE
         // ---- 2. zero-extending W_MOV -> its readers read the source
         {
             uint32_t wwidth[PF_NW + 1];  // width of the value each W register holds now
@@ -544,8 +538,6 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
                 drop[i] = 1;  // dst keeps its old value, which nothing reads before its next write
             }
         }
-#endif
-#ifndef PF_NO_CONST_FUSE
         // ---- 3. W_CONST -> constant operands of its readers
         {
             auto settle = [&](uint32_t r) {
@@ -593,8 +585,6 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
             }
             for (uint32_t r = 0; r <= PF_NW; r++) settle(r);
         }
-#endif
-#ifndef PF_NO_LDS_SPILL
         // ---- 4. spill slots -> LDS entries 1..3 of EXP's window table (PF_SPILL_LDS)
         // A segment is a SPILL of slot k and the FILLs of k before its next SPILL.  One whose
         // range holds no W_EXP takes entry 2 or 3 when free (entry 1 too if no B_UMUL_NOOVF
@@ -642,8 +632,6 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
                 }
             }
         }
-#endif
-#ifndef PF_NO_FORWARD
         // ---- 5. back-to-back forwarding: an instruction reading the W register the kept
         // instruction right before it wrote takes that result directly (PF_I_FA / PF_I_FB,
         // traffic bit cleared), and the writer skips its write-back (PF_TR_WW cleared) when
@@ -681,7 +669,6 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
                 if (!live) pw0 &= ~(PF_TR_WW << 18);
             }
         }
-#endif
         const size_t first = code_out.size() / 4;
         size_t kept = 0;
         for (uint32_t i = 0; i < n; i++) kept += !drop[i];
@@ -701,13 +688,11 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
 // instruction counts): one for small batches (a single query's), up to 8 for large ones.
 std::vector<size_t> prep_ranges(const pf_set_desc* descs, size_t n_sets, size_t n_ins) {
     size_t nt = 1;
-#ifndef PF_PREP_SERIAL
     if (n_sets >= 64 && n_ins >= (1u << 15)) {
         // hardware_concurrency reads sysfs: once per process, and not on a small batch's path
         static const size_t hw = std::max<size_t>(1, std::thread::hardware_concurrency());
         nt = std::min<size_t>({8, hw, n_sets / 32});
     }
-#endif
     std::vector<size_t> cut(nt + 1, n_sets);
     cut[0] = 0;
     uint64_t total = 0, acc = 0;
@@ -1221,16 +1206,12 @@ int pf_batch_free(uint64_t handle) {
     Batch* B = as_batch(handle);
     if (!B) return 0;
     Dev* D = use_dev(B->device);
-#ifdef PF_FREE_DEVICE_SYNC
-    hipDeviceSynchronize();
-#else
     // a *_dev launch may still be reading the batch on a caller's stream: drain the stream of
     // the device's last launch (switch_stream has drained every earlier one; the library's
     // own launches are complete when their call returns, and the upload's copy when
     // pf_batch_create returned).  A whole-device synchronisation here cost every
     // single-query call a device-wide round trip.
     if (D && D->last_stream) hipStreamSynchronize(D->last_stream);
-#endif
     if (D) D->last_stream = nullptr;
     release_batch(D, B);
     return 0;
@@ -1576,26 +1557,8 @@ int pf_keccak256_fixed_dev(const uint8_t* d_data, uint32_t len, size_t n, uint8_
     if (switch_stream(D, st)) return -1;
     HIPCHK(hipEventRecord(D->ev0, st));
     const bool fast = (len % 16u) == 0u && len < 136u && (((uintptr_t)d_data) & 15u) == 0u;
-#ifdef PF_KECCAK_PERSIST
-    if (fast && len == 64u) {
-        // chip-filling persistent grid: PF_KECCAK_PERSIST 256-thread blocks per CU
-        const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, (uint64_t)D->num_cus * PF_KECCAK_PERSIST);
-        hipLaunchKernelGGL(pf_keccak_fixed64_persist_kernel, dim3((uint32_t)blocks), dim3(256), 0,
-                           st, d_data, (uint64_t)n, d_out32);
-    } else
-#endif
-#ifdef PF_KECCAK_ILP2
-    if (fast)
-        hipLaunchKernelGGL(pf_keccak_fixed2_kernel, dim3((uint32_t)(((n + 1) / 2 + 255) / 256)), dim3(256), 0,
-                           st, d_data, len, (uint64_t)n, d_out32);
-    else
-#endif
-    if (fast)
-        hipLaunchKernelGGL(pf_keccak_fixed_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0,
-                           st, d_data, len, (uint64_t)n, d_out32);
-    else
-        hipLaunchKernelGGL(pf_keccak_stride_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256),
-                           0, st, d_data, len, (uint64_t)n, d_out32);
+    hipLaunchKernelGGL(fast ? pf_keccak_fixed_kernel : pf_keccak_stride_kernel,
+                       dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_data, len, (uint64_t)n, d_out32);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(D->ev1, st));
     if (kernel_ms) {

@@ -54,45 +54,16 @@ namespace {
         _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)                                    \
             (dst).l[k_] = (W)[k_ / (LPB)][(r) * (LPB) + (k_ % (LPB))];                         \
     } while (0)
-// The 8-register kernels read and write registers through a uniform switch over the
-// register number instead: static VGPR indices, no indexing mode (config 3 +0.8 %, and 8
-// VGPRs fewer: 155).  The 16-register kernels keep s_set_gpr_idx (a 16-way switch per
+// Narrow kernels: the register file is PF_NW_NARROW x 8 plain scalars, read and written
+// through a uniform switch over the register number (RDN_SW / WRN_SW), so every access is a
+// static VGPR index with no indexing mode and each limb is its own VGPR (no 16-dword vector
+// tuples, no write sink).  The 16-register kernels keep s_set_gpr_idx (a 16-way switch per
 // operand is a lot of code for the 0.4 % of sets that run them).
-#define RD_CASE(dst, W, R, LPB)                                                            \
-    case R:                                                                               \
-        _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)                                  \
-            (dst).l[k_] = (W)[k_ / (LPB)][(R) * (LPB) + (k_ % (LPB))];                     \
-        break;
-#define RD_SW(dst, W, r, LPB)                                                              \
-    do {                                                                                  \
-        switch (r) {                                                                      \
-            RD_CASE(dst, W, 0, LPB) RD_CASE(dst, W, 1, LPB) RD_CASE(dst, W, 2, LPB)       \
-            RD_CASE(dst, W, 3, LPB) RD_CASE(dst, W, 4, LPB) RD_CASE(dst, W, 5, LPB)       \
-            default: RD_CASE(dst, W, 6, LPB)                                              \
-        }                                                                                 \
-    } while (0)
-#define WR_CASE(W, R, src, LPB)                                                            \
-    case R:                                                                               \
-        _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)                                  \
-            (W)[k_ / (LPB)][(R) * (LPB) + (k_ % (LPB))] = (src).l[k_];                     \
-        break;
-#define WR_SW(W, r, src, LPB)                                                              \
-    do {                                                                                  \
-        switch (r) {                                                                      \
-            WR_CASE(W, 0, src, LPB) WR_CASE(W, 1, src, LPB) WR_CASE(W, 2, src, LPB)       \
-            WR_CASE(W, 3, src, LPB) WR_CASE(W, 4, src, LPB) WR_CASE(W, 5, src, LPB)       \
-            WR_CASE(W, 6, src, LPB) default: WR_CASE(W, 7, src, LPB)                      \
-        }                                                                                 \
-    } while (0)
-// Narrow kernels: the register file is PF_NW_NARROW x 8 plain scalars, every access a
-// static index under a uniform switch over the register number, so each limb is its own
-// VGPR (no 16-dword vector tuples, no write sink): 56 VGPRs for 7 registers.
 // The operand copy is one asm block per case: as plain assignments, the phi copies of a
 // case were placed before the compare that leaves it (critical edges are not split), so a
 // read of register 2 executed the copies of registers 0, 1 and 2 (24 v_mov, ~14 on average
 // over the register mix instead of 8).  Early-clobber outputs: the moves run in order.
-#ifndef PF_RD_PLAIN
-#define PF_MOV8(d, s)                                                                        \
+#define PF_MOV8(d, s)                                                                       \
     asm("v_mov_b32 %0, %8\n\tv_mov_b32 %1, %9\n\tv_mov_b32 %2, %10\n\tv_mov_b32 %3, %11\n\t"     \
         "v_mov_b32 %4, %12\n\tv_mov_b32 %5, %13\n\tv_mov_b32 %6, %14\n\tv_mov_b32 %7, %15"          \
         : "=&v"((d).l[0]), "=&v"((d).l[1]), "=&v"((d).l[2]), "=&v"((d).l[3]), "=&v"((d).l[4]),     \
@@ -103,32 +74,11 @@ namespace {
     case R:                                                                               \
         PF_MOV8(dst, (W)[R]);                                                             \
         break;
-#else
-#define RDN_CASE(dst, W, R)                                                                \
-    case R:                                                                               \
-        _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)(dst).l[k_] = (W)[R][k_];          \
-        break;
-#endif
 #define WRN_CASE(W, R, src)                                                                \
     case R:                                                                               \
         _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)(W)[R][k_] = (src).l[k_];          \
         break;
-// Where the next instruction's fetch is issued.  Default: right after this instruction's
-// decode, before its operand reads.  PF_FETCH_LATE issues it after the operand reads, with an
-// explicit lgkmcnt(0) after each LDS operand read: LDS reads and scalar loads share lgkmcnt
-// and scalar loads return out of order, so with the early fetch the compiler's wait at the
-// join of the operand switch also waits for the fetch in flight.  Measured on config 3
-// (round 4, two A/B pairs on one box): the late fetch is 1.9 % SLOWER (14.54 vs 14.26 ms) —
-// the fetch latency the early issue exposes at that join is smaller than what it hides.
-#ifndef PF_FETCH_LATE
-#define PF_FETCH_EARLY
-#endif
-#ifndef PF_FETCH_EARLY
-#define PF_WAIT_LDS() __builtin_amdgcn_s_waitcnt(0xC07F)  // lgkmcnt(0)
-#else
-#define PF_WAIT_LDS() ((void)0)
-#endif
-#if PF_NW_NARROW == 7
+static_assert(PF_NW_NARROW == 7, "RDN_SW / WRN_SW place registers 0..4 in VGPRs and 5, 6 in LDS");
 // Registers 5 and 6 live in LDS, one 32-byte slot per lane each: entry 0 of EXP's window
 // table (which keeps base^0 = 1 out of it) and one entry past it (PF_LDS_WREG6).  40 VGPRs of
 // register file is what lets the kernel run 4 waves per SIMD without spilling; the lowering
@@ -139,8 +89,8 @@ namespace {
         switch (r) {                                                                      \
             RDN_CASE(dst, W, 0) RDN_CASE(dst, W, 1) RDN_CASE(dst, W, 2) RDN_CASE(dst, W, 3) \
             RDN_CASE(dst, W, 4)                                                           \
-            case 5: (dst) = pf::tbl_get(LT, 64u, PF_LDS_WREG5); PF_WAIT_LDS(); break;       \
-            default: (dst) = pf::tbl_get(LT, 64u, PF_LDS_WREG6); PF_WAIT_LDS(); break;      \
+            case 5: (dst) = pf::tbl_get(LT, 64u, PF_LDS_WREG5); break;                      \
+            default: (dst) = pf::tbl_get(LT, 64u, PF_LDS_WREG6); break;                     \
         }                                                                                 \
     } while (0)
 #define WRN_SW(W, r, src, LT)                                                              \
@@ -155,24 +105,6 @@ namespace {
 #if PF_EXP_SPLIT > 32
 #error "the narrow kernels' LDS registers need exp256_w32 (PF_EXP_SPLIT <= 32)"
 #endif
-#elif PF_NW_NARROW == 6
-#define RDN_SW(dst, W, r, LT)                                                                  \
-    do {                                                                                  \
-        switch (r) {                                                                      \
-            RDN_CASE(dst, W, 0) RDN_CASE(dst, W, 1) RDN_CASE(dst, W, 2) RDN_CASE(dst, W, 3) \
-            RDN_CASE(dst, W, 4) default: RDN_CASE(dst, W, 5)                              \
-        }                                                                                 \
-    } while (0)
-#define WRN_SW(W, r, src, LT)                                                              \
-    do {                                                                                  \
-        switch (r) {                                                                      \
-            WRN_CASE(W, 0, src) WRN_CASE(W, 1, src) WRN_CASE(W, 2, src) WRN_CASE(W, 3, src) \
-            WRN_CASE(W, 4, src) default: WRN_CASE(W, 5, src)                              \
-        }                                                                                 \
-    } while (0)
-#else
-#error "PF_NW_NARROW must be 6 or 7"
-#endif
 #define WR_W(W, r, src, LPB)                                                                  \
     do {                                                                                      \
         _Pragma("unroll") for (int k_ = 0; k_ < 8; k_++)                                    \
@@ -185,13 +117,6 @@ namespace {
 // write-back, where lgkmcnt(0) also waits for the next instruction's scalar fetch issued at
 // the top of this one — every bytecode instruction then paid the fetch latency.
 #define PF_WAIT_ALL() __builtin_amdgcn_s_waitcnt(0)
-// vector-memory loads only (vmcnt(0) expcnt(7) lgkmcnt(15)): the generator's loads are
-// vector gathers, and lgkmcnt would also wait for the next instruction's scalar fetch
-#ifdef PF_GEN_WAIT_VM
-#define PF_WAIT_GEN() __builtin_amdgcn_s_waitcnt(0x0F70)
-#else
-#define PF_WAIT_GEN() PF_WAIT_ALL()
-#endif
 
 // per-limb mask for width w.  w is wave-uniform (it comes from the scalar-loaded
 // instruction); the mask is formed from the top limb index and its partial mask with
@@ -269,19 +194,6 @@ PF_INL u256 pow2m1(uint32_t k) {  // 2^k - 1
     }
     return r;
 }
-
-#if defined(PF_PROBE_2X_GEN) || defined(PF_PROBE_2X_DIV) || defined(PF_PROBE_2X_EXP) || \
-    defined(PF_PROBE_2X_MUL) || defined(PF_PROBE_2X_PHILOX)
-// Doubling probes (timing only, tools/gpu_probe2x.sh): a unit runs twice on operands that
-// differ by a per-lane zero the compiler cannot see through, and the second result is folded
-// in under that zero — same values, same branches, twice the unit's issue.  The time added is
-// the unit's marginal cost in the running kernel, without the value shift of a removal probe.
-PF_INL uint32_t hidden_zero() {
-    uint32_t z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-#endif
 
 // boundary-arm deltas (gen_var): entry j in bits 3j..3j+2, biased by 2
 #define PF_BND_DELTA 0x2ca281b1aull
@@ -368,19 +280,7 @@ PF_INL uint32_t umod_rcp(uint32_t x, uint32_t d, uint32_t z) {
 PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
     const uint4 sc = S.schema[v];  // uniform -> scalar load
     const uint64_t p0 = mul_wide(cand, PF_PHILOX_M0);  // round 1 of all three blocks
-#ifdef PF_PROBE_2X_PHILOX
-    uint4 m = philox_gen(p0, v, 2u, S.k0, S.k1);
-    const uint32_t hzp = hidden_zero();
-    {
-        const uint64_t p0b = mul_wide(cand ^ hzp, PF_PHILOX_M0);
-        const uint4 mb = philox_gen(p0b, v, 2u, S.k0, S.k1);
-        const uint4 r0b = philox_gen(p0b, v, 0u, S.k0, S.k1);
-        const uint4 r1b = philox_gen(p0b, v, 1u, S.k0, S.k1);
-        m.w ^= (mb.w ^ r0b.x ^ r1b.y) & hzp;
-    }
-#else
     const uint4 m = philox_gen(p0, v, 2u, S.k0, S.k1);
-#endif
     const uint32_t kind = sc.x & 0xffu, w = (sc.x >> 8) & 0x3ffu;
     const uint32_t hint0 = sc.y, hint1 = sc.z, pslot = sc.w;
     // The one per-lane gather (a constant of the set for the +-1 arm, or the actor table
@@ -393,26 +293,13 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
     const uint32_t ci = S.n_const ? umod_rcp(m.y, S.n_const, S.nc_rcp) : 0u;
     const uint32_t* gp = S.consts + (size_t)(act ? hint0 + ai : ci) * 8u;
     u256 g;
-#ifdef PF_DIAG_NO_GATHER  // timing probe only: the per-lane gather's cost
-    g = pf::zero256(); g.l[0] = (uint32_t)(size_t)gp;
-#else
 #pragma unroll
     for (int i = 0; i < 8; i++) g.l[i] = gp[i];
-#endif
     const uint4 r0 = philox_gen(p0, v, 0u, S.k0, S.k1);
     // r1 only feeds limbs 4..7 of the random arm, which the final mask clears for w <= 128
     // (bytes, selectors, small counters): skipped there under a wave-uniform branch
     uint4 r1 = make_uint4(0u, 0u, 0u, 0u);
-#ifdef PF_DIAG_R1_CHEAP  // timing probe only (wrong values): limbs 4..7 from a cheap mix of r0
-    if (w > 128u) {
-        r1.x = __umulhi(r0.x ^ 0x9E3779B9u, 0xD2511F53u) ^ r0.w;
-        r1.y = __umulhi(r0.y ^ 0x7F4A7C15u, 0xCD9E8D57u) ^ r0.x;
-        r1.z = __umulhi(r0.z ^ 0x85EBCA6Bu, 0xD2511F53u) ^ r0.y;
-        r1.w = __umulhi(r0.w ^ 0xC2B2AE35u, 0xCD9E8D57u) ^ r0.z;
-    }
-#else
     if (w > 128u) r1 = philox_gen(p0, v, 1u, S.k0, S.k1);
-#endif
     const bool has_parent = pslot != PF_NO_PARENT;
     u256 par = pf::zero256();
     if (has_parent) {
@@ -437,12 +324,10 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
         out = pf::add256(base, k);
     } else if (kind == PF_VK_SMALL) {
         out.l[0] = (hint0 == 0xffffffffu) ? r0.x : (r0.x % (hint0 + 1u));
-#ifndef PF_DIAG_NO_LASER_ARMS
         if (hint0 >= 4u && hint0 != 0xffffffffu) {  // uniform: ABI-aligned sizes in half the lanes
             const uint32_t al = 4u + 32u * (r0.y % ((hint0 - 4u) / 32u + 1u));
             out.l[0] = (m.x & 16u) ? al : out.l[0];
         }
-#endif
     } else if (kind == PF_VK_BOOL) {
         out.l[0] = r0.x & 1u;
     } else {
@@ -501,7 +386,6 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
             // the actor set (transaction/symbolic.py:215) in most lanes
             out.l[i] = act ? g.l[i] : out.l[i];
         }
-#ifndef PF_DIAG_NO_LASER_ARMS  // timing probe only: the LASER-aware arms compiled out
         if (kind == PF_VK_VALUE) {  // uniform: call values are 0 in half the lanes
 #pragma unroll
             for (int i = 0; i < 8; i++) out.l[i] = (m.x & 16u) ? 0u : out.l[i];
@@ -533,7 +417,6 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
                 out.l[0] = (u & 1u) ? byte : out.l[0];
             }
         }
-#endif
     }
     // the parent model itself (candidate 0) and its neighbourhood (odd candidates keep the
     // parent value of most variables)
@@ -578,12 +461,9 @@ PF_INL void prof_add(UnitProf* P, uint32_t b, uint64_t dt) {
 PF_INL uint2* exp_tbl_of(uint2* lds) {
     return lds + (threadIdx.x >> 6) * (PF_LDS_ENTRIES * 4 * 64) + (threadIdx.x & 63u);
 }
-#ifndef PF_WG_PER_CU_NARROW
+// workgroups per CU the search kernels are bounded for: narrow (8-register) and wide
 #define PF_WG_PER_CU_NARROW 4
-#endif
-#ifndef PF_WG_PER_CU
 #define PF_WG_PER_CU 2
-#endif
 
 // Run one set's program for this lane's candidate.  Returns the lane's root (0/1);
 // *complete = 1 if the program ran to END (not short-circuited).  `ops` accumulates
@@ -601,14 +481,8 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
     uint32_t Bk = 0u;
     // spill slots (lowering under register pressure): dynamically indexed, so the compiler
     // keeps them in private scratch memory, never in the VGPR banks
-    // physical spill slot of bytecode slot k (PF_SPILL_ROT: rotated by the wave's hardware
-    // slot, a probe of how the scratch lines of the 4096 waves share the L2)
-#ifdef PF_SPILL_ROT
-    const uint32_t spill_rot = __builtin_amdgcn_readfirstlane(blockIdx.x);
-#define PF_SLOT(k) (((k) + spill_rot) & (PF_MAX_SPILL - 1u))
-#else
+    // physical spill slot of bytecode slot k
 #define PF_SLOT(k) ((k) & (PF_MAX_SPILL - 1u))
-#endif
 // Extra private dwords per lane.  The spill slots live in each wave's scratch window, and
 // with 2,064 B per lane the windows are 0x20400 bytes apart, so the slot-0 lines of the 4,096
 // resident waves collided in the L2 and were evicted to memory: WRITE_SIZE 115 MB per
@@ -616,13 +490,9 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 // per lane (window 0x24400) halves it, 53 MB, at the same speed (profiles/r04e_*, r04f_*:
 // pads of 32 B .. 1 KB and a per-wave slot rotation all land at 53–64 MB); the rest is the
 // spill stores themselves (PF_VAR_SPILL_USES=3: 31 MB at -0.4 %, =99: 11 MB at -0.9 %).
-#ifndef PF_SPILL_PAD
 #define PF_SPILL_PAD 64
-#endif
     uint32_t spill[PF_MAX_SPILL * 8 + PF_SPILL_PAD];
-#if PF_SPILL_PAD
     if (__builtin_expect(cand == 0xFFFFFFFFu, 0)) spill[PF_MAX_SPILL * 8 + PF_SPILL_PAD - 1] = 0u;  // keep the pad
-#endif
 #define BGET(r) ((Bk >> ((r) & 31u)) & 1u)
 #define BSET(r, v) (Bk = (Bk & ~(1u << ((r) & 31u))) | (((v) & 1u) << ((r) & 31u)))
     // Ops with a B result (compares, bool logic, B_VAR, UMUL_NOOVF) set their bit and skip
@@ -664,15 +534,6 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
     // peephole sets them only on the instruction right after a W write; nothing writes z in
     // between — B ops and the narrow W_SPILL leave before the write-back)
     u256 z;
-#ifndef PF_NO_FORWARD
-#define PF_FWD_A() else if (I.x & PF_I_FA) x = z
-#define PF_FWD_B() else if (I.x & PF_I_FB) y = z
-#define PF_FWD_WB(tr) __builtin_expect(((tr) & PF_TR_WW) != 0u, 1)
-#else
-#define PF_FWD_A() else {}
-#define PF_FWD_B() else {}
-#define PF_FWD_WB(tr) true
-#endif
     for (;;) {
 #ifdef PF_PROFILE_UNITS
         {
@@ -699,30 +560,27 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
         // of the unit dispatch below, not a test of its own on every instruction: it reads
         // no operand (traffic bits 0) and its fetch of the slot after it stays inside the
         // batch (pf_batch_create pads the code region by one instruction)
-#ifdef PF_END_TEST
-        if (__builtin_expect(unit == PF_U_END, 0)) break;
-#endif
         // Issue the next fetch only after this instruction's words are decoded: scalar
         // loads return out of order, so a fetch issued before the decode would be waited
-        // for together with the one being consumed (lgkmcnt(0)).  And after the operand
-        // reads (PF_WAIT_LDS): see there.
-#ifdef PF_FETCH_EARLY
+        // for together with the one being consumed (lgkmcnt(0)).  It goes before the operand
+        // reads: the LDS reads of registers 5 and 6 share lgkmcnt with it, but the latency
+        // the early issue hides is larger than what it exposes at the operand switch's join.
         __builtin_amdgcn_sched_barrier(0);
         In = fetch_ins(++ip);
-#endif
         u256 x, y;
         // register indices are trusted: pf_batch_create checks every read and write
-        // against the register file of the kernel that runs the set
+        // against the register file of the kernel that runs the set.  An operand flagged
+        // PF_I_FA / PF_I_FB is the previous W result, still in z.
         if (NREG == 8) {
             if (__builtin_expect((tr & PF_TR_RA) != 0u, 1)) RDN_SW(x, Wn, a, exp_tbl);
-            PF_FWD_A();
+            else if (I.x & PF_I_FA) x = z;
             if (__builtin_expect((tr & PF_TR_RB) != 0u, 1)) RDN_SW(y, Wn, b, exp_tbl);
-            PF_FWD_B();
+            else if (I.x & PF_I_FB) y = z;
         } else {
             if (__builtin_expect((tr & PF_TR_RA) != 0u, 1)) RD_W(x, W, a, LPB);
-            PF_FWD_A();
+            else if (I.x & PF_I_FA) x = z;
             if (__builtin_expect((tr & PF_TR_RB) != 0u, 1)) RD_W(y, W, b, LPB);
-            PF_FWD_B();
+            else if (I.x & PF_I_FB) y = z;
         }
         // constant operands (pf_batch_create's peephole deleted their W_CONST): one scalar
         // load of const[a] / const[b] each
@@ -738,54 +596,24 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 for (int i = 0; i < 8; i++) y.l[i] = cp[i];
             }
         }
-#ifndef PF_FETCH_EARLY
-        __builtin_amdgcn_sched_barrier(0);
-        In = fetch_ins(++ip);
-#endif
         // Dispatch on the datapath unit (w0 bits 21..23) first.  The heavy datapaths exist
         // once each (multiplier, divider, shifter, generator) and are shared by every
         // opcode that needs them: the kernel's code must stay small enough for the
         // instruction cache, since consecutive bytecode instructions jump between units.
         switch (unit) {
-#ifndef PF_END_TEST
             case PF_U_END:
                 goto program_end;
-#endif
             case PF_U_MUL:
                 // ---- multiplier: MUL = one product; EXP = windowed square-and-multiply over
                 // the low 84 exponent bits + the 2-adic closed form for bits 84..253
                 // (pf::exp256_split)
                 if (op == PF_W_MUL) {
                     z = pf::mul256(x, y);
-#ifdef PF_PROBE_2X_MUL
-                    {
-                        const uint32_t hz = hidden_zero();
-                        u256 x2 = x;
-                        x2.l[0] ^= hz;
-                        const u256 z2 = pf::mul256(x2, y);
-                        z.l[7] ^= z2.l[7] & hz;
-                    }
-#endif
                 } else {
-#ifdef PF_DIAG_NO_EXP
-                    z = pf::add256(x, y);
-#else
 #ifdef PF_PROFILE_UNITS
                     z = pf::exp256_split(x, y, exp_tbl, 64u, &prof->c[15]);
 #else
-#ifdef PF_PROBE_2X_EXP
-                    {
-                        const uint32_t hz = hidden_zero();
-                        u256 x2 = x;
-                        x2.l[1] ^= hz;
-                        const u256 z2 = pf::exp256_split(x2, y, exp_tbl, 64u);
-                        z = pf::exp256_split(x, y, exp_tbl, 64u);
-                        z.l[7] ^= z2.l[7] & hz;
-                    }
-#else
                     z = pf::exp256_split(x, y, exp_tbl, 64u);
-#endif
-#endif
 #endif
                     PF_WAIT_ALL();
                 }
@@ -821,21 +649,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                             : !pf::wave_any((bz ^ 1u) & (uint32_t)(pf::clz256(ub) > pf::clz256(ua) + 31u)) ? 13u : 14u;
                 }
 #endif
-#ifdef PF_DIAG_NO_DIV
-                q = ua; rr = ub;
-#else
                 pf::udivrem256(ua, ub, &q, &rr);
-#ifdef PF_PROBE_2X_DIV
-                {
-                    const uint32_t hz = hidden_zero();
-                    u256 ua2 = ua, q2, r2;
-                    ua2.l[0] ^= hz;
-                    pf::udivrem256(ua2, ub, &q2, &r2);
-                    q.l[0] ^= q2.l[0] & hz;
-                    rr.l[0] ^= r2.l[7] & hz;
-                }
-#endif
-#endif
                 // x and y are not read past the division (their registers are free in it):
                 // UMUL_NOOVF's a comes back from LDS, SMOD's signed divisor is rebuilt from |b|
                 if (op == PF_B_UMUL_NOOVF) {
@@ -854,9 +668,6 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 break;
             }
             case PF_U_SHIFT: {
-#ifdef PF_DIAG_NO_SHIFT
-                z = pf::add256(x, y); break;
-#endif
                 const bool by_reg = op <= PF_W_ASHR;
                 const uint32_t big = by_reg ? ge_width(y, w) : (aux >= 256u);
                 const uint32_t amt = by_reg ? y.l[0] : aux;
@@ -878,25 +689,13 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
             case PF_U_GEN:
                 // ---- candidate generator (one site for W and B variables)
                 if (MODE == MODE_GEN) {
-#ifdef PF_DIAG_NO_GEN
-                    z = pf::zero256(); z.l[0] = cand ^ aux;
-#else
                     z = gen_var(S, aux, cand);
-#ifdef PF_PROBE_2X_GEN
-                    {
-                        const uint32_t hz = hidden_zero();
-                        const u256 z2 = gen_var(S, aux, cand ^ hz);
-                        z.l[0] ^= z2.l[0] & (hz - 1u) & hz;
-                        z.l[1] ^= z2.l[7] & hz;
-                    }
-#endif
-#endif
                 } else {
 #pragma unroll
                     for (int i = 0; i < 8; i++)
                         z.l[i] = active ? soa[((size_t)aux * 8u + i) * soa_n + cand] : 0u;
                 }
-                PF_WAIT_GEN();
+                PF_WAIT_ALL();
                 if (op == PF_B_VAR) {
                     BSET(d, z.l[0]);
                     PF_NEXT();
@@ -1005,9 +804,6 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                     case PF_W_SEXT: z = sextw(x, aux); break;
                     case PF_W_ITE: z = pf::sel256(BGET(c), x, y); break;
                     case PF_W_HASH: {
-#ifdef PF_DIAG_NO_HASH
-                        z = pf::sub256(x, y); break;
-#endif
                         uint4 h = philox(make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]), aux, PF_HASH_K1A);
                         uint4 g = philox(make_uint4(x.l[4] ^ h.x, x.l[5] ^ h.y, x.l[6] ^ h.z, x.l[7] ^ h.w),
                                          aux, PF_HASH_K1B);
@@ -1029,7 +825,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
             if (NREG == 8) {
                 // only W results reach here (W_SPILL leaves above); PF_TR_WW clear = a result
                 // only the next instruction reads (forwarded), no write-back
-                if (PF_FWD_WB(tr)) WRN_SW(Wn, d, z, exp_tbl);
+                if (__builtin_expect((tr & PF_TR_WW) != 0u, 1)) WRN_SW(Wn, d, z, exp_tbl);
             } else {
                 __builtin_amdgcn_sched_barrier(0);
                 WR_W(W, dd, z, LPB);
@@ -1042,15 +838,10 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
         (void)prof;
 #endif
     }
-#ifndef PF_END_TEST
 program_end:
-#endif
     *complete = sc ^ 1u;
     *ops += cost;
     return root;
-#undef PF_FWD_A
-#undef PF_FWD_B
-#undef PF_FWD_WB
 #undef BGET
 }
 
@@ -1114,9 +905,6 @@ PF_INL void search_item(const SetCtx& S, uint32_t set, uint32_t begin, uint32_t 
         decided += __popcll(m_act);
         evals_full += __popcll(m_full);
         ops += lane_ops * (uint64_t)__popcll(m_act);
-#ifdef PF_DIAG_ALL_ATOMICS  // timing probe only: one found[] atomic per witnessed group
-        posted = false;
-#endif
         if (m_sat && !posted) {
             uint32_t first = base + (uint32_t)__builtin_ctzll(m_sat);
             if (lane == 0) atomicMin(found + set, first);
@@ -1126,14 +914,9 @@ PF_INL void search_item(const SetCtx& S, uint32_t set, uint32_t begin, uint32_t 
     }
 }
 
-// PF_FULL_QUEUE (default 1): the full sweep also runs as the persistent work queue (items
-// set-major, sets longest first; +2 % on config 3 against one wave per item, which
-// PF_FULL_QUEUE=0 restores)
-#ifndef PF_FULL_QUEUE
-#define PF_FULL_QUEUE 1
-#endif
 // ---- search kernel: generate + evaluate + ballot early exit ---------------------------
-// grid: one wave per (set, slice); a slice is `per_wave` consecutive candidates.
+// grid: a chip-filling set of persistent waves that take (set, slice) items from a work
+// queue; a slice is `per_wave` consecutive candidates.
 // Two entry points over one body: the full sweep (pf_check_kernel) and the production
 // early-exit search (pf_check_early_kernel).  EARLY is a template constant so the full sweep
 // carries no found[] polling, and the two launches are separate rows in a rocprof trace.
@@ -1149,7 +932,6 @@ PF_INL void check_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const uint32_t n_items = n_sets * slices;
-    if (!EARLY && !PF_FULL_QUEUE && wave >= n_items) return;
     __shared__ uint2 pf_exp_lds[PF_SEARCH_LDS_U2];
     uint2* exp_tbl = exp_tbl_of(pf_exp_lds);
 
@@ -1174,57 +956,46 @@ PF_INL void check_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
 #endif
     uint64_t evals_full = 0, decided = 0, ops = 0;
     uint32_t cut = 0u;
-    // Full sweep: one wave per (set, slice), set-major (a set's slices side by side, sets
-    // longest first).  Early exit: a work queue of (set, chunk) items in chunk-major order —
-    // chunk 0 of every set first, then chunk 1, ... — taken one at a time by a chip-filling
-    // grid of waves.  A witness found in a low chunk makes the set's later chunks cost one
-    // found[] read each, instead of every concurrently launched slice of the set evaluating
-    // at least one group, and no wave idles while items remain (dynamic balance).  The
-    // smallest-witness result does not depend on the order: a chunk stops only once a witness
-    // below its own range exists.  Every wave leaves the loop: the queue head only grows.
-    if (!EARLY && !PF_FULL_QUEUE) {
-        const uint32_t set = __builtin_amdgcn_readfirstlane(order[wave / slices]);
-        const uint32_t slice = wave % slices;
-        search_item<EARLY, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), set,
-                                 cand_begin + slice * per_wave, min(budget, cand_begin + slice * per_wave + per_wave), flags,
-                                 deadline_ticks, t0, found, exp_tbl, evals_full, decided, ops, cut, prof);
-    } else {
-        // PF_EARLY_QUEUES heads, 128 B apart: queue q hands out items q, q + Q, q + 2Q, ...
-        // (so the claims stay close to chunk-major order overall); a wave starts at queue
-        // wave % Q and moves on to the next queue when one runs dry.  One head serialised the
-        // claims at ~14 ns each in L2 — the whole cost of a planted batch, whose items after
-        // the first chunk are all skips.  Each inner loop ends because its head only grows.
-        for (uint32_t qi = 0; qi < PF_EARLY_QUEUES; ++qi) {
-            const uint32_t q = (wave + qi) % PF_EARLY_QUEUES;
-            const uint32_t nq = n_items > q ? (n_items - q + PF_EARLY_QUEUES - 1u) / PF_EARLY_QUEUES : 0u;
-#ifndef PF_QUEUE_NO_PEEK
-            // another wave's queue is read before it is claimed from: once the items run out,
-            // every wave passes every queue on its way out, and as atomics those probes
-            // serialise on the 16 heads (~14 ns each: ~60 us for a 4,096-wave grid, the
-            // larger part of a small batch's search); a plain load of a drained head does not
-            if (qi > 0u) {
-                uint32_t h = 0u;
-                if (lane == 0u) h = __hip_atomic_load(queue + q * PF_EARLY_QUEUE_STRIDE, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-                if (__builtin_amdgcn_readfirstlane(h) >= nq) continue;
-            }
-#endif
-            for (;;) {
-                uint32_t v = 0u;
-                if (lane == 0u) v = atomicAdd(queue + q * PF_EARLY_QUEUE_STRIDE, 1u);
-                const uint32_t k = __builtin_amdgcn_readfirstlane(v);
-                if (k >= nq) break;
-                const uint32_t item = k * PF_EARLY_QUEUES + q;
-                // early exit: chunk-major; full sweep: set-major, sets longest first
-                const uint32_t set = __builtin_amdgcn_readfirstlane(order[EARLY ? item % n_sets : item / slices]);
-                const uint32_t slice = EARLY ? item / n_sets : item % slices;
-                search_item<EARLY, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), set,
-                                         cand_begin + slice * per_wave, min(budget, cand_begin + slice * per_wave + per_wave), flags,
-                                         deadline_ticks, t0, found, exp_tbl, evals_full, decided, ops, cut, prof);
-                if (cut) break;
-            }
+    // A work queue of (set, slice) items taken one at a time by a chip-filling grid of waves,
+    // so no wave idles while items remain (dynamic balance).  Full sweep: items set-major (a
+    // set's slices side by side, sets longest first).  Early exit: chunk-major — chunk 0 of
+    // every set first, then chunk 1, ...: a witness found in a low chunk makes the set's
+    // later chunks cost one found[] read each, instead of every concurrently launched slice
+    // of the set evaluating at least one group.  The smallest-witness result does not depend
+    // on the order: a chunk stops only once a witness below its own range exists.
+    // PF_EARLY_QUEUES heads, 128 B apart: queue q hands out items q, q + Q, q + 2Q, ...
+    // (so the claims stay close to chunk-major order overall); a wave starts at queue
+    // wave % Q and moves on to the next queue when one runs dry.  One head serialised the
+    // claims at ~14 ns each in L2 — the whole cost of a planted batch, whose items after
+    // the first chunk are all skips.  Each inner loop ends because its head only grows.
+    for (uint32_t qi = 0; qi < PF_EARLY_QUEUES; ++qi) {
+        const uint32_t q = (wave + qi) % PF_EARLY_QUEUES;
+        const uint32_t nq = n_items > q ? (n_items - q + PF_EARLY_QUEUES - 1u) / PF_EARLY_QUEUES : 0u;
+        // another wave's queue is read before it is claimed from: once the items run out,
+        // every wave passes every queue on its way out, and as atomics those probes
+        // serialise on the 16 heads (~14 ns each: ~60 us for a 4,096-wave grid, the
+        // larger part of a small batch's search); a plain load of a drained head does not
+        if (qi > 0u) {
+            uint32_t h = 0u;
+            if (lane == 0u) h = __hip_atomic_load(queue + q * PF_EARLY_QUEUE_STRIDE, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(h) >= nq) continue;
+        }
+        for (;;) {
+            uint32_t v = 0u;
+            if (lane == 0u) v = atomicAdd(queue + q * PF_EARLY_QUEUE_STRIDE, 1u);
+            const uint32_t k = __builtin_amdgcn_readfirstlane(v);
+            if (k >= nq) break;
+            const uint32_t item = k * PF_EARLY_QUEUES + q;
+            // early exit: chunk-major; full sweep: set-major, sets longest first
+            const uint32_t set = __builtin_amdgcn_readfirstlane(order[EARLY ? item % n_sets : item / slices]);
+            const uint32_t slice = EARLY ? item / n_sets : item % slices;
+            search_item<EARLY, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), set,
+                                     cand_begin + slice * per_wave, min(budget, cand_begin + slice * per_wave + per_wave), flags,
+                                     deadline_ticks, t0, found, exp_tbl, evals_full, decided, ops, cut, prof);
             if (cut) break;
         }
+        if (cut) break;
     }
     if (lane == 0) {
         unsigned long long* cs = counters + PF_COUNTER_OFF / 8 + (wave % PF_COUNTER_STRIPES) * 16u;

@@ -85,19 +85,6 @@ __device__ __forceinline__ void keccak_round(Lane a[25], uint32_t rc_lo, uint32_
     }
 #pragma unroll
     for (int x = 0; x < 5; x++) R[x] = rotl<1>(C[(x + 1) % 5]);
-#ifdef PF_KECCAK_THETA2
-    // D[x] = C[x-1] ^ rot1(C[x+1]) once per column, then two-source xors into the 25 lanes:
-    // 10 + 50 two-source ops instead of 50 three-source ones
-#pragma unroll
-    for (int x = 0; x < 5; x++) {
-        const uint32_t dlo = C[(x + 4) % 5].lo ^ R[x].lo, dhi = C[(x + 4) % 5].hi ^ R[x].hi;
-#pragma unroll
-        for (int y = 0; y < 25; y += 5) {
-            a[x + y].lo ^= dlo;
-            a[x + y].hi ^= dhi;
-        }
-    }
-#else
 #pragma unroll
     for (int x = 0; x < 5; x++)
 #pragma unroll
@@ -105,7 +92,6 @@ __device__ __forceinline__ void keccak_round(Lane a[25], uint32_t rc_lo, uint32_
             a[x + y].lo = xor3(a[x + y].lo, C[(x + 4) % 5].lo, R[x].lo);
             a[x + y].hi = xor3(a[x + y].hi, C[(x + 4) % 5].hi, R[x].hi);
         }
-#endif
     // rho + pi
     Lane t = a[1];
     rho_pi_step<0>(a, t);
@@ -221,93 +207,6 @@ pf_keccak_stride_kernel(const uint8_t* __restrict__ data, uint32_t len, uint64_t
     if (i >= n) return;
     absorb_and_squeeze(stage + threadIdx.x, data + i * (uint64_t)len, len, out32 + 32 * i);
 }
-
-// Persistent form of the fixed-length fast path (PF_KECCAK_PERSIST): a chip-filling grid in
-// which every lane walks messages i, i + stride, ...; the next message's 16-byte chunks are
-// loaded while the current permutation runs, so a wave's load latency overlaps its own
-// VALU work instead of relying on other waves alone.
-// NQ: 16-byte chunks per message (4 for the 64-byte key||slot preimages), a template so the
-// prefetch buffer holds only the chunks that exist
-template <int NQ>
-__device__ __forceinline__ void keccak_persist(const uint8_t* __restrict__ data, uint32_t len, uint64_t n,
-                                               uint8_t* __restrict__ out32) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr uint32_t nq = NQ;
-    uint4 nxt[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; k++)
-        nxt[k] = i < n ? ((const uint4*)(data + i * (uint64_t)len))[k] : make_uint4(0u, 0u, 0u, 0u);
-    for (; i < n; i += stride) {
-        Lane a[25];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint4 v = k < NQ ? nxt[k < NQ ? k : 0] : make_uint4(0u, 0u, 0u, 0u);
-            a[2 * k] = Lane{v.x, v.y};
-            a[2 * k + 1] = Lane{v.z, v.w};
-        }
-        const uint64_t j = i + stride;
-#pragma unroll
-        for (int k = 0; k < NQ; k++)
-            nxt[k] = j < n ? ((const uint4*)(data + j * (uint64_t)len))[k] : make_uint4(0u, 0u, 0u, 0u);
-        a[16] = Lane{0u, 0x80000000u};
-#pragma unroll
-        for (int k = 17; k < 25; k++) a[k] = Lane{0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 17; k++)
-            if ((uint32_t)k == (len >> 3)) a[k].lo ^= 0x01u;
-        keccakf<true>(a);
-        squeeze(a, out32 + 32 * i);
-    }
-}
-
-// the 64-byte key||slot preimages (config 4); other lengths take pf_keccak_fixed_kernel
-extern "C" __global__ void __launch_bounds__(256)
-pf_keccak_fixed64_persist_kernel(const uint8_t* __restrict__ data, uint64_t n, uint8_t* __restrict__ out32) {
-    keccak_persist<4>(data, 64u, n, out32);
-}
-
-#ifdef PF_KECCAK_ILP2
-// Probe (PF_KECCAK_ILP2): two messages per lane, i and i + ceil(n/2), their permutations
-// interleaved round by round — two independent dependency chains per wave instead of one.
-__device__ __forceinline__ void load_fixed(Lane a[25], const uint8_t* __restrict__ data, uint32_t len,
-                                           uint64_t i, bool live) {
-    const uint4* q = (const uint4*)(data + i * (uint64_t)len);
-    const uint32_t nq = len >> 4;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        uint4 v = (live && (uint32_t)k < nq) ? q[k] : make_uint4(0u, 0u, 0u, 0u);
-        a[2 * k] = Lane{v.x, v.y};
-        a[2 * k + 1] = Lane{v.z, v.w};
-    }
-    a[16] = Lane{0u, 0x80000000u};
-#pragma unroll
-    for (int k = 17; k < 25; k++) a[k] = Lane{0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 17; k++)
-        if ((uint32_t)k == (len >> 3)) a[k].lo ^= 0x01u;
-}
-
-extern "C" __global__ void __launch_bounds__(256)
-pf_keccak_fixed2_kernel(const uint8_t* __restrict__ data, uint32_t len, uint64_t n,
-                        uint8_t* __restrict__ out32) {
-    const uint64_t half = (n + 1) / 2;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= half) return;
-    const uint64_t j = i + half;
-    const bool has_j = j < n;
-    Lane a[25], b[25];
-    load_fixed(a, data, len, i, true);
-    load_fixed(b, data, len, has_j ? j : i, has_j);
-#pragma unroll
-    for (int rnd = 0; rnd < 24; rnd++) {
-        keccak_round(a, kRC[2 * rnd], kRC[2 * rnd + 1]);
-        keccak_round(b, kRC[2 * rnd], kRC[2 * rnd + 1]);
-    }
-    squeeze(a, out32 + 32 * i);
-    if (has_j) squeeze(b, out32 + 32 * j);
-}
-#endif
 
 // fixed-length single-block fast path: the host launches it when len % 16 == 0,
 // len < 136 and the buffer is 16-byte aligned (16-byte vector loads, two 16-byte digest

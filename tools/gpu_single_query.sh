@@ -1,6 +1,6 @@
 # The bench's discharge leg (corpus batch, hints-off, live order, single-query sample) alone,
 # once per environment setting ("base" = defaults), each its own process.
-# usage: bash tools/gpu_single_query.sh TAG base ENV=VALUE lib:NAME ...  (lib: build_var/lib_NAME.so)
+# usage: bash tools/gpu_single_query.sh TAG base ENV=VALUE lib:PATH ...  (lib: bench.py --lib PATH)
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${1:-sq}; shift
@@ -12,7 +12,7 @@ for rep in 1 2; do
 for v in "$@"; do
   i=$((i+1))
   E=""; L=""
-  if [ "${v#lib:}" != "$v" ]; then L="--lib build_var/lib_${v#lib:}.so"; elif [ "$v" != base ]; then E="$v"; fi
+  if [ "${v#lib:}" != "$v" ]; then L="--lib ${v#lib:}"; elif [ "$v" != base ]; then E="$v"; fi
   timeout -k 10 300 env $E $B $L > $O/sq$i.log 2>&1 || { echo "variant $v failed"; tail -5 $O/sq$i.log; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/sq$i.log').read().strip().splitlines()[-1])['discharge']

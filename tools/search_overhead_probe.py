@@ -21,7 +21,7 @@ from mythril_amd.engine import get_engine  # noqa: E402
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-    if len(sys.argv) > 2:  # an alternative build (tools/build_variants.sh)
+    if len(sys.argv) > 2:  # an alternative build of libpathfeas.so
         _lib.load_library(sys.argv[2])
     eng = get_engine()
     flags = ir.FLAG_EARLY_EXIT | ir.FLAG_SHORTCIRCUIT

@@ -79,7 +79,9 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
                        size_t n_sets, uint64_t* handle_out);
 
 /* Host only (no device call; for tests): the program pf_batch_create puts on the device for
- * this batch — traffic/unit bits recomputed, then its peepholes (an ASSERT folded into the
+ * this batch — traffic/unit bits recomputed, then the fold pass (mythril_amd/csrc/pf_fold.h;
+ * PF_DEVICE_FOLD is read on every call: 0 = off, 2 = the fold pass alone; pf_batch_create
+ * itself folds only batches of 16 sets or more) and its peepholes (an ASSERT folded into the
  * compare before it, PF_I_ASSERT; a W_CONST folded into its readers, PF_I_KA / PF_I_KB, only
  * when its constant fits the W_CONST's width — consts may be NULL: all taken to fit).
  * code_out: room for n_ins instructions; descs_out: n_sets entries (code ranges shifted). */

@@ -20,6 +20,7 @@
 
 #include "../../include/pathfeas.h"
 #include "pf_eval.hip"
+#include "pf_fold.h"
 #include "pf_keccak.hip"
 
 namespace {
@@ -85,6 +86,24 @@ uint32_t g_early_chunk_groups = 8;
 // a host hint model that leaves a root false — the probe of a long program then only delays
 // the search behind it; profiles/r06_probe_rule.md).
 uint32_t g_probe_max_sets = 64;
+// PF_DEVICE_FOLD: the device program's fold pass (pf_fold.h).  0 = off, 1 = on (default),
+// 2 = the fold pass alone, without the peepholes after it (its output is still a lowered
+// program, so tests can feed it back in).  pf_batch_create takes the value read at init,
+// pf_device_program reads it on every call.
+// pf_batch_create folds only batches of PF_FOLD_MIN_SETS sets or more.  The walk costs ~19 ns
+// per instruction on the host (corpus batch, 1,023 sets / 507,856 instructions: 2.6 -> 3.9 ms)
+// and pays back over the candidates a set is swept with; a single query's batch is one or two
+// buckets of ~500 instructions searched with early exit, and its upload phase grew from 0.073
+// to 0.083 ms (run-to-run spread 0.001) for no search time back (profiles/r07_fold_ab.md).
+// No program length makes the walk free, so the gate is the batch's set count.
+int g_device_fold = 1;
+constexpr size_t PF_FOLD_MIN_SETS = 16;
+int device_fold_env() {
+    const char* e = getenv("PF_DEVICE_FOLD");
+    if (!e || !*e) return 1;
+    const long v = strtol(e, nullptr, 10);
+    return v >= 0 && v <= 2 ? (int)v : 1;
+}
 
 int fail(const char* fmt, ...) {
     char buf[512];
@@ -421,12 +440,19 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
     return 0;
 }
 
-// The device form of a validated batch (traffic / unit bits already set): three
+// The device form of a validated batch (traffic / unit bits already set): a fold pass and
 // semantics-preserving peepholes rewrite the program the kernel runs, never the caller's
 // arrays (the oracles evaluate the program as lowered).  Each set is rewritten in a scratch
 // copy (descriptors may share or reorder code ranges) and appended to code_out; every pass is
 // one forward walk with per-register state.  Shared by pf_batch_create and the host-only test
 // export pf_device_program.
+//  0. fold (pf_fold.h, PF_DEVICE_FOLD): results that are the same for every candidate —
+//     constant operands, x-op-x identities, absorbing and neutral constants — become a W_MOV,
+//     W_CONST, B_CONST or W_XOR r, r, and what only they needed is dropped (liveness from the
+//     ASSERTs).  The passes below clean up after it (its W_MOVs and W_CONSTs mostly vanish).
+//     aux1 of every dropped instruction, here or below, moves to the next kept one: a wave
+//     leaves a program only at an assert, so `ops` counts what it counted for the lowered
+//     program (the counter contract).
 //  1. ASSERT: folded into the last writer of its B register when that is a compare or bool op
 //     (PF_I_ASSERT) — the conjunction's value does not depend on where the and happens, and
 //     with PF_FLAG_SHORTCIRCUIT an earlier check only exits sooner (round 2 folded it only
@@ -459,8 +485,9 @@ bool const_fits(const uint32_t* consts, size_t n_const, uint32_t idx, uint32_t w
 // Sets [s0, s1) of the batch: their device programs appended to code_out, each set's
 // code_off rewritten to its offset in code_out.
 void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& descs_out, size_t s0, size_t s1,
-                          std::vector<uint32_t>& code_out, const uint32_t* consts, size_t n_const) {
+                          std::vector<uint32_t>& code_out, const uint32_t* consts, size_t n_const, int fold) {
     std::vector<uint32_t> P;      // the set being rewritten
+    pf_fold::Scratch fold_scratch;
     std::vector<uint8_t> drop;
     struct Pending {              // pass 3: the W_CONST a register holds, and its readers
         int64_t at = -1;
@@ -474,11 +501,18 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
         P.assign(code_fixed + 4 * (size_t)d.code_off, code_fixed + 4 * ((size_t)d.code_off + n));
         drop.assign(n, 0);
         auto tr_of = [&](uint32_t i) { return (P[4 * i] >> 18) & 7u; };
+        // ---- 0. constants, identities and dead code
+        if (fold) {
+            const bool pool = consts && (uint64_t)d.const_off + d.n_const <= n_const;
+            pf_fold::fold_program(P.data(), n, drop.data(), pool ? consts + 8 * (size_t)d.const_off : nullptr,
+                                  pool ? d.n_const : 0u, fold_scratch);
+        }
         // ---- 1. ASSERT -> PF_I_ASSERT on the last writer of its register
-        {
+        if (fold != 2) {
             int64_t last_b[PF_NB];
             for (int r = 0; r < PF_NB; r++) last_b[r] = -1;
             for (uint32_t i = 0; i < n; i++) {
+                if (drop[i]) continue;
                 const uint32_t op = P[4 * i] & 0xffu;
                 if (op == PF_ASSERT) {
                     const int64_t k = last_b[(P[4 * i + 1] >> 8) & 31u];
@@ -495,7 +529,7 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
             }
         }
         // ---- 2. zero-extending W_MOV -> its readers read the source
-        {
+        if (fold != 2) {
             uint32_t wwidth[PF_NW + 1];  // width of the value each W register holds now
             for (int r = 0; r <= PF_NW; r++) wwidth[r] = 0xffffffffu;
             for (uint32_t i = 0; i < n; i++) {
@@ -539,7 +573,7 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
             }
         }
         // ---- 3. W_CONST -> constant operands of its readers
-        {
+        if (fold != 2) {
             auto settle = [&](uint32_t r) {
                 Pending& q = pend[r];
                 if (q.at >= 0 && q.ok && !q.readers.empty()) {
@@ -590,7 +624,7 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
         // range holds no W_EXP takes entry 2 or 3 when free (entry 1 too if no B_UMUL_NOOVF
         // runs in it): the value never touches scratch.  Entries are handed out in program
         // order; a segment without a FILL stays (a dead store costs nothing more).
-        {
+        if (fold != 2) {
             struct Seg {
                 uint32_t spill, last;
                 std::vector<uint32_t> fills;
@@ -636,7 +670,7 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
         // instruction right before it wrote takes that result directly (PF_I_FA / PF_I_FB,
         // traffic bit cleared), and the writer skips its write-back (PF_TR_WW cleared) when
         // no later instruction reads the register before its next write
-        {
+        if (fold != 2) {
             int64_t prev = -1;
             for (uint32_t q = 0; q < n; q++) {
                 if (drop[q]) continue;
@@ -674,11 +708,17 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
         for (uint32_t i = 0; i < n; i++) kept += !drop[i];
         code_out.resize(4 * (first + kept));
         uint32_t* o = code_out.data() + 4 * first;
-        for (uint32_t i = 0; i < n; i++)
-            if (!drop[i]) {
-                memcpy(o, P.data() + 4 * (size_t)i, 16);
-                o += 4;
+        uint32_t carry = 0;  // aux1 of the dropped instructions since the last kept one
+        for (uint32_t i = 0; i < n; i++) {
+            if (drop[i]) {
+                carry += P[4 * (size_t)i + 3];
+                continue;
             }
+            memcpy(o, P.data() + 4 * (size_t)i, 16);
+            o[3] += carry;
+            carry = 0;
+            o += 4;
+        }
         d.code_off = (uint32_t)first;
         d.n_ins = (uint32_t)kept;
     }
@@ -718,17 +758,17 @@ void run_ranges(size_t n, F&& fn) {
 // own thread), then concatenated in set order — the program one pass over all sets gives.
 void device_program(const uint32_t* code_fixed, size_t n_fixed, std::vector<pf_set_desc>& descs_out,
                     const std::vector<size_t>& cut, std::vector<uint32_t>& code_out, const uint32_t* consts,
-                    size_t n_const) {
+                    size_t n_const, int fold) {
     const size_t nt = cut.size() - 1;
     code_out.clear();
     if (nt == 1) {
         code_out.reserve(n_fixed);
-        device_program_range(code_fixed, descs_out, 0, descs_out.size(), code_out, consts, n_const);
+        device_program_range(code_fixed, descs_out, 0, descs_out.size(), code_out, consts, n_const, fold);
         return;
     }
     std::vector<std::vector<uint32_t>> outs(nt);
     run_ranges(nt, [&](size_t t) {
-        device_program_range(code_fixed, descs_out, cut[t], cut[t + 1], outs[t], consts, n_const);
+        device_program_range(code_fixed, descs_out, cut[t], cut[t + 1], outs[t], consts, n_const, fold);
     });
     size_t total = 0;
     for (const auto& o : outs) total += o.size();
@@ -747,7 +787,8 @@ extern "C" {
 int pf_version(void) { return 2; }
 
 // Host only (no HIP call, tests/test_device_program.py): the program pf_batch_create would put
-// on the device — traffic / unit bits recomputed from the opcodes, then the peepholes.
+// on the device — traffic / unit bits recomputed from the opcodes, then the fold pass (whatever
+// the batch's size: pf_batch_create skips it below PF_FOLD_MIN_SETS sets) and the peepholes.
 // code_out needs room for n_ins instructions (the peepholes only delete); descs_out n_sets.
 int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
                       const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
@@ -760,7 +801,8 @@ int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts
     }
     std::vector<pf_set_desc> d(descs, descs + n_sets);
     std::vector<uint32_t> out;
-    device_program(fixed.data(), fixed.size(), d, prep_ranges(descs, n_sets, n_ins), out, consts, n_const);
+    device_program(fixed.data(), fixed.size(), d, prep_ranges(descs, n_sets, n_ins), out, consts, n_const,
+                   device_fold_env());
     memcpy(code_out, out.data(), out.size() * 4);
     *n_ins_out = out.size() / 4;
     memcpy(descs_out, d.data(), n_sets * sizeof(pf_set_desc));
@@ -807,8 +849,10 @@ void warm_unwinder() {
     });
 }
 
-// launch-geometry knobs from the environment, read by both initialisers
+// launch-geometry knobs and the device-program fold switch from the environment, read by
+// both initialisers
 void read_env_knobs() {
+    g_device_fold = device_fold_env();
     if (const char* e = getenv("PF_WAVES_PER_CU")) {
         long v = strtol(e, nullptr, 10);
         if (v >= 8 && v <= 4096) g_waves_per_cu_full = g_waves_per_cu_early = (uint32_t)v;
@@ -1024,7 +1068,8 @@ static int prepare_program(const uint32_t* code, size_t n_ins, const uint32_t* c
                           wide.data()))
                 return -1;
     }
-    device_program(code_fixed.data(), code_fixed.size(), descs_out, cut, code_out, consts, n_const);
+    device_program(code_fixed.data(), code_fixed.size(), descs_out, cut, code_out, consts, n_const,
+                   n_sets >= PF_FOLD_MIN_SETS ? g_device_fold : 0);
     return 0;
 }
 

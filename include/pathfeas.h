@@ -88,6 +88,19 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
 int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
                       const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
                       pf_set_desc* descs_out);
+/* Host only: what pf_batch_create uploads for this batch.  Batches of 16 sets or more are
+ * folded (pf_batch_create's gate), and a W result the fold pass knows to be a constant that
+ * is neither 0 nor in the set's pool becomes a W_CONST of a constant of the device program's
+ * own.  consts_out receives the device pool: the caller's n_const constants verbatim, then, for
+ * every set with constants of its own, that set's constants again followed by its new ones;
+ * descs_out[s].const_off points at the set's range there and n_const stays the caller's count
+ * (the candidate generator draws from the constants it drew from before).  code_out is
+ * readable only against consts_out.  consts_out: room for consts_cap constants; *n_const_out
+ * is the pool's size, and the call fails, nothing written, when that is more.  A W_CONST
+ * index above 255 is never folded into its readers (PF_I_KA / PF_I_KB hold 8 bits).         */
+int pf_device_batch(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
+                    const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
+                    pf_set_desc* descs_out, uint32_t* consts_out, size_t consts_cap, size_t* n_const_out);
 int pf_batch_free(uint64_t handle);
 
 /* Generate candidates [0, budget) on device for every set and search for a witness.

@@ -73,6 +73,8 @@ SIGNATURES = {
     "pf_eval_assignments_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "pf_device_program": (ctypes.c_int, [_u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p, ctypes.POINTER(_sz), _u32p]),
+    "pf_device_batch": (ctypes.c_int, [_u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p, ctypes.POINTER(_sz), _u32p,
+                                       _u32p, _sz, ctypes.POINTER(_sz)]),
     "pf_keccak256_batch": (ctypes.c_int, [_u8p, _u64p, _sz, _u8p]),
     "pf_keccak256_fixed_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _sz,
                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_float),
@@ -194,3 +196,22 @@ def ptr_u8(a: np.ndarray):
 def ptr_u64(a: np.ndarray):
     assert a.dtype == np.uint64
     return _ptr(a, _U64_1, _u64p)
+
+
+def device_batch(code, consts, descs):
+    """pf_device_batch (host only): what pf_batch_create uploads for a batch's ``code`` (n x 4),
+    ``consts`` (n x 8) and ``descs`` (n x 8) — the device programs, their descriptors and the
+    device constant pool those index (the caller's constants, then the sets' own)."""
+    L = lib()
+    code = np.ascontiguousarray(code, dtype=np.uint32)
+    descs = np.ascontiguousarray(descs, dtype=np.uint32)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    out, dout = np.zeros_like(code), np.zeros_like(descs)
+    # at most one new constant per instruction, and one copy of a set's range per set
+    cap = len(consts) + int(descs[:, 3].sum()) + len(code)
+    pool = np.zeros((max(cap, 1), 8), dtype=np.uint32)
+    n, nc = ctypes.c_size_t(), ctypes.c_size_t()
+    check(L.pf_device_batch(ptr_u32(code), len(code), ptr_u32(consts) if consts.size else None, len(consts),
+                            ptr_u32(descs), len(descs), ptr_u32(out), ctypes.byref(n), ptr_u32(dout),
+                            ptr_u32(pool), cap, ctypes.byref(nc)), "pf_device_batch")
+    return out[:n.value], dout, pool[:nc.value]

@@ -447,9 +447,10 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
 // one forward walk with per-register state.  Shared by pf_batch_create and the host-only test
 // export pf_device_program.
 //  0. fold (pf_fold.h, PF_DEVICE_FOLD): results that are the same for every candidate —
-//     constant operands, x-op-x identities, absorbing and neutral constants — become a W_MOV,
-//     W_CONST, B_CONST or W_XOR r, r, and what only they needed is dropped (liveness from the
-//     ASSERTs).  The passes below clean up after it (its W_MOVs and W_CONSTs mostly vanish).
+//     constant operands, x-op-x identities, absorbing and neutral constants, compares and
+//     divisions a value's range decides — become a W_MOV, W_CONST (of the set's pool, or of a
+//     constant of the program's own: OwnConsts below), B_CONST or W_XOR r, r, and what only
+//     they needed is dropped (liveness from the ASSERTs).  The passes below clean up after it (its W_MOVs and W_CONSTs mostly vanish).
 //     aux1 of every dropped instruction, here or below, moves to the next kept one: a wave
 //     leaves a program only at an assert, so `ops` counts what it counted for the lowered
 //     program (the counter contract).
@@ -482,10 +483,20 @@ bool const_fits(const uint32_t* consts, size_t n_const, uint32_t idx, uint32_t w
     return true;
 }
 
+// Constants of the device programs' own (pf_fold.h: a constant result that is neither 0 nor in
+// the set's pool): vals holds 8 u32 each in set order, cnt[s] how many set s has.  Their indices
+// follow the set's own n_const constants (device_pool lays the pool out that way).
+struct OwnConsts {
+    std::vector<uint32_t> vals;
+    std::vector<uint32_t> cnt;
+};
+
 // Sets [s0, s1) of the batch: their device programs appended to code_out, each set's
-// code_off rewritten to its offset in code_out.
+// code_off rewritten to its offset in code_out.  own (may be null: pf_device_program, whose
+// result is read against the caller's pool) collects the sets' own constants.
 void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& descs_out, size_t s0, size_t s1,
-                          std::vector<uint32_t>& code_out, const uint32_t* consts, size_t n_const, int fold) {
+                          std::vector<uint32_t>& code_out, const uint32_t* consts, size_t n_const, int fold,
+                          OwnConsts* own = nullptr) {
     std::vector<uint32_t> P;      // the set being rewritten
     pf_fold::Scratch fold_scratch;
     std::vector<uint8_t> drop;
@@ -504,8 +515,12 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
         // ---- 0. constants, identities and dead code
         if (fold) {
             const bool pool = consts && (uint64_t)d.const_off + d.n_const <= n_const;
+            // a set without constants has a pool all the same: the empty one
+            const bool own_ok = own && (pool || (d.n_const == 0 && d.const_off <= n_const));
+            const size_t before = own ? own->vals.size() : 0;
             pf_fold::fold_program(P.data(), n, drop.data(), pool ? consts + 8 * (size_t)d.const_off : nullptr,
-                                  pool ? d.n_const : 0u, fold_scratch);
+                                  pool ? d.n_const : 0u, fold_scratch, own_ok ? &own->vals : nullptr);
+            if (own) own->cnt[s] = (uint32_t)((own->vals.size() - before) / 8);
         }
         // ---- 1. ASSERT -> PF_I_ASSERT on the last writer of its register
         if (fold != 2) {
@@ -612,8 +627,10 @@ void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& 
                 }
                 if ((tr & PF_TR_WW) && rd <= PF_NW) {
                     settle(rd);
+                    // (a constant of the program's own is below 2^w of the instruction it replaced)
                     if (op == PF_W_CONST && P[4 * i + 2] <= 0xffu &&
-                        const_fits(consts, n_const, d.const_off + P[4 * i + 2], (P[4 * i] >> 8) & 0x3ffu))
+                        ((own && P[4 * i + 2] >= d.n_const) ||
+                         const_fits(consts, n_const, d.const_off + P[4 * i + 2], (P[4 * i] >> 8) & 0x3ffu)))
                         pend[rd].at = i;
                 }
             }
@@ -756,27 +773,58 @@ void run_ranges(size_t n, F&& fn) {
 
 // The device program of every set: each range of `cut` rewritten into its own buffer (on its
 // own thread), then concatenated in set order — the program one pass over all sets gives.
+// pool_out (may be null: no constants of the programs' own) receives the device constant pool
+// when it differs from the caller's (else it is left empty): the caller's n_const constants verbatim, then, for every set that gained constants of its
+// own, that set's constants again followed by the new ones, with the set's const_off pointing
+// there.  n_const of the descriptors stays the caller's count — the candidate generator
+// draws from [const_off, const_off + n_const) and sees the constants it saw before — and a set
+// without new constants keeps its range.
 void device_program(const uint32_t* code_fixed, size_t n_fixed, std::vector<pf_set_desc>& descs_out,
                     const std::vector<size_t>& cut, std::vector<uint32_t>& code_out, const uint32_t* consts,
-                    size_t n_const, int fold) {
-    const size_t nt = cut.size() - 1;
+                    size_t n_const, int fold, std::vector<uint32_t>* pool_out = nullptr) {
+    const size_t nt = cut.size() - 1, n_sets = descs_out.size();
     code_out.clear();
+    const bool owning = pool_out && fold;
+    std::vector<OwnConsts> own(owning ? nt : 0);
+    for (OwnConsts& o : own) o.cnt.assign(n_sets, 0);
     if (nt == 1) {
         code_out.reserve(n_fixed);
-        device_program_range(code_fixed, descs_out, 0, descs_out.size(), code_out, consts, n_const, fold);
-        return;
+        device_program_range(code_fixed, descs_out, 0, n_sets, code_out, consts, n_const, fold,
+                             owning ? &own[0] : nullptr);
+    } else {
+        std::vector<std::vector<uint32_t>> outs(nt);
+        run_ranges(nt, [&](size_t t) {
+            device_program_range(code_fixed, descs_out, cut[t], cut[t + 1], outs[t], consts, n_const, fold,
+                                 owning ? &own[t] : nullptr);
+        });
+        size_t total = 0;
+        for (const auto& o : outs) total += o.size();
+        code_out.reserve(total);
+        for (size_t t = 0; t < nt; t++) {
+            const uint32_t base = (uint32_t)(code_out.size() / 4);
+            for (size_t s = cut[t]; s < cut[t + 1]; s++) descs_out[s].code_off += base;
+            code_out.insert(code_out.end(), outs[t].begin(), outs[t].end());
+        }
     }
-    std::vector<std::vector<uint32_t>> outs(nt);
-    run_ranges(nt, [&](size_t t) {
-        device_program_range(code_fixed, descs_out, cut[t], cut[t + 1], outs[t], consts, n_const, fold);
-    });
-    size_t total = 0;
-    for (const auto& o : outs) total += o.size();
-    code_out.reserve(total);
-    for (size_t t = 0; t < nt; t++) {
-        const uint32_t base = (uint32_t)(code_out.size() / 4);
-        for (size_t s = cut[t]; s < cut[t + 1]; s++) descs_out[s].code_off += base;
-        code_out.insert(code_out.end(), outs[t].begin(), outs[t].end());
+    if (!pool_out) return;
+    pool_out->clear();
+    size_t n_own = 0;
+    for (const OwnConsts& o : own) n_own += o.vals.size();
+    if (!n_own) return;  // left empty: the device pool is the caller's, no copy
+    if (consts) pool_out->assign(consts, consts + 8 * n_const);
+    for (size_t t = 0; t < own.size(); t++) {
+        const uint32_t* v = own[t].vals.data();
+        for (size_t s = cut[t]; s < cut[t + 1]; s++) {
+            const uint32_t k = own[t].cnt[s];
+            if (!k) continue;
+            pf_set_desc& d = descs_out[s];
+            const uint32_t at = (uint32_t)(pool_out->size() / 8);
+            if (d.n_const) pool_out->insert(pool_out->end(), consts + 8 * (size_t)d.const_off,
+                                            consts + 8 * ((size_t)d.const_off + d.n_const));
+            pool_out->insert(pool_out->end(), v, v + 8 * (size_t)k);
+            v += 8 * (size_t)k;
+            d.const_off = at;
+        }
     }
 }
 
@@ -806,6 +854,39 @@ int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts
     memcpy(code_out, out.data(), out.size() * 4);
     *n_ins_out = out.size() / 4;
     memcpy(descs_out, d.data(), n_sets * sizeof(pf_set_desc));
+    return 0;
+}
+
+// Host only: what pf_batch_create uploads for this batch — the device programs, the device
+// constant pool they index (device_program: the caller's constants, then the sets' own) and
+// the descriptors with code_off and const_off re-based.  Unlike pf_device_program it applies
+// pf_batch_create's PF_FOLD_MIN_SETS gate, and its code is readable only against consts_out.
+// PF_DEVICE_FOLD is read on every call.  consts_out has room for consts_cap constants;
+// *n_const_out is the pool's size, and a smaller consts_cap fails with nothing written.
+int pf_device_batch(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
+                    const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
+                    pf_set_desc* descs_out, uint32_t* consts_out, size_t consts_cap, size_t* n_const_out) {
+    std::vector<uint32_t> fixed(code, code + 4 * n_ins);
+    for (size_t i = 0; i < n_ins; i++) {
+        uint32_t* I = fixed.data() + 4 * i;
+        const uint32_t op = I[0] & 0xffu;
+        I[0] = (I[0] & 0x3ffffu) | (pf_op_traffic(op) << 18) | (pf_op_unit(op) << 21);
+    }
+    std::vector<pf_set_desc> d(descs, descs + n_sets);
+    std::vector<uint32_t> out, pool;
+    device_program(fixed.data(), fixed.size(), d, prep_ranges(descs, n_sets, n_ins), out, consts, n_const,
+                   n_sets >= PF_FOLD_MIN_SETS ? device_fold_env() : 0, &pool);
+    const uint32_t* pc = pool.empty() ? consts : pool.data();
+    const size_t np = pool.empty() ? n_const : pool.size() / 8;
+    *n_const_out = np;
+    if (np > consts_cap) {
+        std::lock_guard<std::mutex> lk(g_mu);
+        return fail("pf_device_batch: the device pool holds %zu constants, room for %zu", np, consts_cap);
+    }
+    memcpy(code_out, out.data(), out.size() * 4);
+    *n_ins_out = out.size() / 4;
+    memcpy(descs_out, d.data(), n_sets * sizeof(pf_set_desc));
+    if (np && pc) memcpy(consts_out, pc, np * 32);
     return 0;
 }
 
@@ -1032,8 +1113,9 @@ static int check_set(size_t s, const uint32_t* code, size_t n_ins, size_t n_cons
 
 // Host-side checks of packed programs and their device form (pf_batch_create and
 // pf_eval_program): every kernel index is derived from these, so nothing the caller packed is
-// trusted.  Fills the device program (device_program), the per-set wide flags and the largest
-// variable count; returns 0 or fail().  A large batch (the corpus pass: 1,023 sets, 376k
+// trusted.  Fills the device program and the device constant pool (device_program; fold: the
+// PF_DEVICE_FOLD value, applied to batches of PF_FOLD_MIN_SETS sets or more), the per-set wide
+// flags and the largest variable count; returns 0 or fail().  A large batch (the corpus pass: 1,023 sets, 376k
 // instructions, ~10 ms on one host thread) is checked and rewritten in set ranges on host
 // threads, each range's device program appended to its own buffer, then concatenated in set
 // order — the same program as the serial pass; a range that fails sends the whole batch
@@ -1041,7 +1123,8 @@ static int check_set(size_t s, const uint32_t* code, size_t n_ins, size_t n_cons
 static int prepare_program(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
                            const uint32_t* schema, size_t n_vars, size_t n_parents, const pf_set_desc* descs,
                            size_t n_sets, std::vector<uint32_t>& code_out, std::vector<pf_set_desc>& descs_out,
-                           std::vector<uint8_t>& wide, uint32_t& max_vars) {
+                           std::vector<uint32_t>& pool_out, std::vector<uint8_t>& wide, uint32_t& max_vars,
+                           int fold) {
     max_vars = 0;
     for (size_t s = 0; s < n_sets; s++) max_vars = std::max(max_vars, descs[s].n_vars);
     std::vector<uint32_t> code_fixed(4 * n_ins);
@@ -1069,7 +1152,7 @@ static int prepare_program(const uint32_t* code, size_t n_ins, const uint32_t* c
                 return -1;
     }
     device_program(code_fixed.data(), code_fixed.size(), descs_out, cut, code_out, consts, n_const,
-                   n_sets >= PF_FOLD_MIN_SETS ? g_device_fold : 0);
+                   n_sets >= PF_FOLD_MIN_SETS ? fold : 0, &pool_out);
     return 0;
 }
 
@@ -1083,11 +1166,12 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     // the lock until its results are back.
     std::vector<uint32_t> code_out;
     std::vector<pf_set_desc> descs_out;
+    std::vector<uint32_t> pool_out;
     std::vector<uint8_t> wide;
     uint32_t max_vars = 0;
     t_defer_err = true;
     const int prc = prepare_program(code, n_ins, consts, n_const, schema, n_vars, n_parents, descs, n_sets,
-                                    code_out, descs_out, wide, max_vars);
+                                    code_out, descs_out, pool_out, wide, max_vars, g_device_fold);
     t_defer_err = false;
     if (prc) {
         std::lock_guard<std::mutex> lk(g_mu);
@@ -1097,6 +1181,12 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     code = code_out.data();
     n_ins = code_out.size() / 4;
     descs = descs_out.data();
+    // the device pool: the caller's constants, then the sets' own (device_program); every
+    // const_off below and on the device is an offset into it
+    if (!pool_out.empty()) {
+        consts = pool_out.data();
+        n_const = pool_out.size() / 8;
+    }
     // Longest-first wave order: waves are dispatched in index order, so mapping the first
     // waves to the most expensive sets leaves the cheap ones for the last, partly filled
     // round.  Weights are measured SIMD cycles per instruction relative to a cheap op
@@ -1471,11 +1561,16 @@ static int eval_programs(const char* who, int device, const uint32_t* code, size
     if (n_sets > 65535) return fail("%s: %zu programs (at most 65535)", who, n_sets);
     std::vector<uint32_t> code_out;
     std::vector<pf_set_desc> descs_out;
+    std::vector<uint32_t> pool_out;
     std::vector<uint8_t> wide;
     uint32_t max_vars = 0;
-    if (prepare_program(code, n_ins, consts, n_const, schema, n_vars, 0, descs, n_sets, code_out, descs_out, wide,
-                        max_vars))
+    if (prepare_program(code, n_ins, consts, n_const, schema, n_vars, 0, descs, n_sets, code_out, descs_out,
+                        pool_out, wide, max_vars, g_device_fold))
         return -1;
+    if (!pool_out.empty()) {  // the device pool (device_program): descs_out index into it
+        consts = pool_out.data();
+        n_const = pool_out.size() / 8;
+    }
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t nv = std::max<size_t>(n_vars, 1), n_dev = code_out.size() / 4, n_out = n_sets * (size_t)n_cand;
     const size_t soa_bytes = nv * 8 * (size_t)n_cand * 4;

@@ -883,6 +883,12 @@ PF_INL void search_item(const SetCtx& S, uint32_t set, uint32_t begin, uint32_t 
     bool posted = false;
     for (uint32_t base = begin; base < end; base += 64u) {
         if (EARLY) {
+            // A program the host folded to a bare END holds for every candidate, so candidate 0
+            // is its witness and every later group has a witness below it — known here without
+            // found[].  Such a wave ends in well under the time the grid takes to start, so
+            // whether a later slice already saw the post in found[] depended on its place in
+            // the launch, and cands_decided / evals_full moved from run to run by a few groups.
+            if (S.n_ins == 1u && base > 0u) break;
             uint32_t f = __hip_atomic_load(found + set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__builtin_amdgcn_readfirstlane(f) <= base) break;
         }

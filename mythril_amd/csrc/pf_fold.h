@@ -12,11 +12,26 @@
  *   constant B result         -> B_CONST
  *   constant W result         -> W_CONST idx when the pool holds the value,
  *                                W_XOR d, r, r when it is 0 (r: a register a kept instruction
- *                                wrote), else the instruction stays and its operands stay live
+ *                                wrote), else W_CONST of a constant of the device program's own
+ *                                when the caller collects them (`extra`: pf_batch_create's
+ *                                device pool, the set's constants followed by these), else the
+ *                                instruction stays and its operands stay live
  *   ASSERT of constant true   -> dropped (a constant false stays)
  * A backward walk from the ASSERTs then drops every instruction whose W, B or spill result no
  * kept instruction reads before its next write.  Values the rewrite cannot express still
  * feed the folds downstream.
+ *
+ * Ranges.  Every value carries a bound: it is below 2^bound.  A constant's is its bit length;
+ * an unknown result's follows from its operands' (result_bound) and is the instruction's
+ * width where nothing better is known.  A result with bound 0 is the constant 0, and the
+ * bound decides (x: bound p, c: a constant, all unsigned):
+ *   0 <= x, x <= c for c >= 2^p - 1                      -> true
+ *   x < 0, M(w) < x                                      -> false
+ *   c >= 2^p:  x < c, x <= c -> true;  x == c, c == x, c < x, c <= x -> false
+ *   signed < and <=: as the unsigned ones when both sides are below 2^(w-1)
+ *   UADD_NOOVF of two values below 2^(w-1)               -> true
+ *   x / c -> 0 and x % c -> x for c >= 2^p;  x & c -> x when c has bits 0..p-1 set;
+ *   x >> c -> 0 for c >= p
  *
  * Every rule holds at every width 1..256 and under the total-division conventions of
  * include/pf_bytecode.h.  A rule is applied only where the operands fit the instruction's
@@ -264,9 +279,10 @@ struct Scratch {
     WV W[16];
     BV B[PF_NB];
     SV S[PF_MAX_SPILL];
-    std::vector<uint8_t> zero;      // instruction i: a constant-0 W result waiting for its register
+    std::vector<uint8_t> zero;      // instruction i: 1 = a constant-0 W result waiting for its register
     std::vector<uint8_t> zreg;      //   an operand register of i to fall back on (0xff: none)
     std::vector<uint16_t> written;  // W registers written before instruction i
+    std::vector<U> own;             // constant results outside the pool, in program order
     struct Key {
         uint32_t opw, a, b, c, aux, vn;
     };
@@ -303,6 +319,50 @@ inline bool is_wbin(uint32_t op) {
 }
 inline bool is_cmp(uint32_t op) { return (op >= PF_B_EQ && op <= PF_B_SLE) || op == PF_B_UADD_NOOVF; }
 
+// The bound of an unknown binary W result from its operands' (both at most w): the value is
+// below 2^bound.  cb: operand b is the constant bv.  Sound under the total-division
+// conventions: x % 0 = x keeps the dividend's bound, x / 0 = M(w) is why a division by an
+// unknown divisor says nothing.
+inline uint32_t result_bound(uint32_t op, uint32_t pa, uint32_t pb, bool cb, const U& bv, uint32_t w) {
+    const uint32_t lo = pa < pb ? pa : pb, hi = pa < pb ? pb : pa;
+    uint32_t bd = w;
+    switch (op) {
+        case PF_W_AND: bd = lo; break;
+        case PF_W_OR:
+        case PF_W_XOR: bd = hi; break;
+        case PF_W_ADD: bd = hi + 1u; break;
+        case PF_W_MUL: bd = pa + pb; break;
+        case PF_W_UREM:
+            bd = pa;
+            if (cb && !uis0(bv) && ubitlen(bv) < bd) bd = ubitlen(bv);
+            break;
+        case PF_W_UDIV:
+            if (cb && !uis0(bv)) bd = pa >= ubitlen(bv) ? pa - ubitlen(bv) + 1u : 0u;
+            break;
+        case PF_W_LSHR:
+            if (cb) bd = pa > ushamt(bv, w) ? pa - ushamt(bv, w) : 0u;
+            break;
+        case PF_W_SHL:
+            if (cb) bd = pa + ushamt(bv, w);
+            break;
+        default: break;
+    }
+    return bd < w ? bd : w;
+}
+
+// B_EQ / B_ULT / B_ULE of an unknown value below 2^p against the constant c, the unknown on
+// the left (x op c) or on the right (c op x): 1 / 0 when the range decides it, else -1
+inline int range_cmp(uint32_t op, bool x_left, uint32_t p, const U& c, uint32_t w) {
+    const bool above = ubitlen(c) > p;  // c >= 2^p
+    if (op == PF_B_EQ) return above ? 0 : -1;
+    if (x_left) {
+        if (op == PF_B_ULT) return uis0(c) ? 0 : above ? 1 : -1;
+        return above || ueq(c, uones(p)) ? 1 : -1;  // x <= c for c >= 2^p - 1
+    }
+    if (op == PF_B_ULE) return uis0(c) ? 1 : above ? 0 : -1;
+    return above || ueq(c, uones(w)) ? 0 : -1;  // c < x
+}
+
 // The pass can reason about the program: it ends with its only END, every opcode is known,
 // every register, slot and width is in range, and no device flag is set yet.
 inline bool well_formed(const uint32_t* P, uint32_t n) {
@@ -331,9 +391,11 @@ inline bool well_formed(const uint32_t* P, uint32_t n) {
 
 // One set's program P (n instructions, traffic / unit bits set) folded in place; drop[i] = 1
 // for every instruction the device program leaves out.  pool: the set's constants (n_pool x 8
-// u32), or null when the caller passed none (then no constant is known).
+// u32), or null when the caller passed none (then no constant is known).  extra (may be null):
+// receives the constants of the device program's own, 8 u32 each; the k-th has index
+// n_pool + k, one entry per value.
 inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t* pool, uint32_t n_pool,
-                         Scratch& T) {
+                         Scratch& T, std::vector<uint32_t>* extra = nullptr) {
     if (!well_formed(P, n)) return;
     // A program that reads no variable stays as lowered.  Its verdict is one constant, which no
     // query sends (z3's simplify and the lowering have folded it away); the per-operation
@@ -363,6 +425,15 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             if (memcmp(pool + 8 * (size_t)k, v.l, 32) == 0) return k;
         return -1;
     };
+    const size_t extra0 = extra ? extra->size() : 0;  // this set's own constants start here
+    auto own_index = [&](const U& v) -> uint32_t {
+        for (size_t k = extra0; k < extra->size(); k += 8)
+            if (memcmp(extra->data() + k, v.l, 32) == 0) return n_pool + (uint32_t)((k - extra0) / 8);
+        extra->insert(extra->end(), v.l, v.l + 8);
+        return n_pool + (uint32_t)((extra->size() - extra0) / 8) - 1u;
+    };
+    constexpr uint8_t OWN_PENDING = 2;  // T.zero[i]: a W_CONST whose aux0 is an entry of T.own, no index yet
+    T.own.clear();
     uint16_t written = 0;
 
     // ---- forward: what every result is, and the rewrites that need no liveness
@@ -386,6 +457,12 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             } else if (uis0(val)) {
                 T.zero[i] = 1;
                 T.zreg[i] = (uint8_t)operand;
+            } else if (extra) {  // its index once the backward walk has kept it
+                I[0] = mk_w0(PF_W_CONST, w);
+                I[1] = d;
+                I[2] = (uint32_t)T.own.size();
+                T.own.push_back(val);
+                T.zero[i] = OWN_PENDING;
             }
         };
         auto w_copy = [&](uint32_t src) {
@@ -449,13 +526,26 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 case PF_W_ASHR: r = za ? ZERO : zb ? CA : NONE; break;
                 default: r = (zb || oa) ? ONE : ob ? CA : NONE; break;  // PF_W_EXP
             }
+            if (r == NONE) {  // the range of the unknown operand against the constant one
+                const bool a_low = ca && ueq(umask(A.v, B.bound), uones(B.bound));
+                const bool b_low = cb && ueq(umask(B.v, A.bound), uones(A.bound));
+                switch (op) {
+                    case PF_W_UDIV: r = cb && ubitlen(B.v) > A.bound ? ZERO : NONE; break;
+                    case PF_W_UREM: r = cb && ubitlen(B.v) > A.bound ? CA : NONE; break;
+                    case PF_W_AND: r = b_low ? CA : a_low ? CB : NONE; break;
+                    case PF_W_LSHR: r = cb && ushamt(B.v, w) >= A.bound ? ZERO : NONE; break;
+                    default: break;
+                }
+            }
+            const uint32_t bd = r == NONE ? result_bound(op, A.bound, B.bound, cb, B.v, w) : w;
+            if (r == NONE && bd == 0) r = ZERO;
             switch (r) {
                 case ZERO: w_const(uzero(), zr); break;
                 case ONE: w_const(usmall(1), zr); break;
                 case ONES: w_const(uones(w), zr); break;
                 case CA: w_copy(a); break;
                 case CB: w_copy(b); break;
-                default: w_unknown(T.number(opw, A.vn, B.vn, 0, 0), w); break;
+                default: w_unknown(T.number(opw, A.vn, B.vn, 0, 0), bd); break;
             }
             continue;
         }
@@ -474,7 +564,15 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             } else if (same && op != PF_B_UADD_NOOVF) {
                 b_const(op == PF_B_EQ || op == PF_B_ULE || op == PF_B_SLE);
             } else {
-                b_unknown(T.number(opw, A.vn, B.vn, 0, 0));
+                // below 2^(w-1) on both sides: no carry out of w bits, and signed order is unsigned order
+                const bool small = A.bound < w && B.bound < w;
+                const uint32_t uop = op == PF_B_SLT ? PF_B_ULT : op == PF_B_SLE ? PF_B_ULE : op;
+                int verdict = -1;
+                if (op == PF_B_UADD_NOOVF) verdict = small ? 1 : -1;
+                else if (A.konst != B.konst && (uop == op || small))
+                    verdict = B.konst ? range_cmp(uop, true, A.bound, B.v, w) : range_cmp(uop, false, B.bound, A.v, w);
+                if (verdict >= 0) b_const(verdict != 0);
+                else b_unknown(T.number(opw, A.vn, B.vn, 0, 0));
             }
             continue;
         }
@@ -506,8 +604,10 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             }
             case PF_W_EXTRACT: {
                 const WV A = T.W[a];
+                const uint32_t bd = A.bound > aux0 ? A.bound - aux0 : 0u;
                 if (A.konst) w_const(umask(ulshr(A.v, aux0), w), a);
-                else w_unknown(T.number(opw, A.vn, 0, 0, aux0), w);
+                else if (bd == 0) w_const(uzero(), a);
+                else w_unknown(T.number(opw, A.vn, 0, 0, aux0), bd < w ? bd : w);
                 break;
             }
             case PF_W_CONCAT: {
@@ -540,7 +640,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 else if (C.konst) w_copy(C.v ? a : b);
                 else if (A.vn == B.vn) w_copy(a);
                 else if (A.konst && B.konst && ueq(A.v, B.v)) w_const(A.v, a);
-                else w_unknown(T.number(opw, A.vn, B.vn, C.vn, 0), w);
+                else w_unknown(T.number(opw, A.vn, B.vn, C.vn, 0), A.bound > B.bound ? A.bound : B.bound);
                 break;
             }
             case PF_W_HASH: w_unknown(T.number(opw, T.W[a].vn, 0, 0, aux0), w); break;
@@ -632,7 +732,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             drop[i] = 1;
             continue;
         }
-        if (T.zero[i]) {
+        if (T.zero[i] == 1) {
             // a register that is live here anyway costs nothing; else an operand of the
             // instruction (one writer stays instead of the datapath op and both)
             const uint32_t free_r = live_w & T.written[i] & ~(1u << d);
@@ -652,6 +752,12 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
         if ((op >= PF_B_AND && op <= PF_B_XOR) || op == PF_B_ITE) live_b |= 1u << b;
         if (op == PF_W_ITE || op == PF_B_ITE) live_b |= 1u << c;
         if (op == PF_W_FILL || op == PF_B_FILL) live_s |= 1ull << I[2];
+    }
+
+    // ---- the kept constants of the program's own get their indices, in program order
+    for (uint32_t i = 0; i + 1 < n && !T.own.empty(); i++) {
+        uint32_t* I = P + 4 * (size_t)i;
+        if (!drop[i] && T.zero[i] == OWN_PENDING) I[2] = own_index(T.own[I[2]]);
     }
 }
 

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Generate mythril_amd/csrc/u256_cols.h: one inline-asm block per product-scanning column.
+"""Generate mythril_amd/csrc/u256_cols.h: one inline-asm block per product-scanning column, and
+the truncated multiply-adds x * y + k mod 2^(32 L), L = 1..7, that EXP's series builds from them
+(tmulk below).
 
 A column accumulates n partial products x_t * y_t into a 64-bit accumulator with
 v_mad_u64_u32; in the carrying form each mad's carry out of bit 63 goes to one of three
@@ -67,9 +69,58 @@ def host_col(n, carry):
     return f"PF_INL void col64_{n}(uint64_t& acc, {args}) {{\n{body}}}\n"
 
 
+def tmulk(L, LY):
+    """x * y + k mod 2^(32 L) from the columns above: x and k have L limbs, y has LY <= L (its
+    limbs >= LY are zero and their products are left out).  The addend rides in the column
+    accumulator: k[0], k[1] are its starting value, and k[c + 2] is added into the word that
+    becomes the accumulator's upper half when column c is shifted out (where a product without
+    an addend moves `hi` there), its carry going to the next `hi`.  A column carries into `hi`
+    while that carry can still reach limb L - 1 (c <= L - 3)."""
+    out = ["template <uint32_t K0, uint32_t K1>",
+           f"PF_INL void tmulk_{L}_{LY}(const uint32_t* x, const uint32_t* y, const uint32_t* k, uint32_t* r) {{"]
+    out.append(f"    uint64_t acc = acc_const<K0, {'K1' if L >= 2 else '0u'}>();")
+    out.append("    uint32_t hi = 0u;")
+    for c in range(L):
+        ts = [t for t in range(c + 1) if c - t < LY]
+        xs = ", ".join(f"x[{t}]" for t in ts)
+        ys = ", ".join(f"y[{c - t}]" for t in ts)
+        carrying = c <= L - 3
+        if ts:
+            out.append(f"    col96_{len(ts)}(acc, hi, {xs}, {ys});" if carrying
+                       else f"    col64_{len(ts)}(acc, {xs}, {ys});")
+        out.append(f"    r[{c}] = (uint32_t)acc;")
+        if c == L - 1:
+            break
+        if carrying:
+            out.append(f"    {{ const uint64_t t = (uint64_t)hi + k[{c + 2}];"
+                       f" acc = (acc >> 32) | (t << 32); hi = (uint32_t)(t >> 32); }}")
+        else:
+            out.append("    acc >>= 32;")
+    out.append("    (void)hi;\n}\n")
+    return "\n".join(out)
+
+
+# The accumulator's constant starting value.  Written as plain C it is a pair of v_mov that the
+# compiler hoists out of every loop of the kernel, one live pair per product, and then spills;
+# the volatile block keeps the two moves where the product is.
+ACC_CONST = """template <uint32_t K0, uint32_t K1>
+PF_INL uint64_t acc_const() {
+#ifndef PF_HOST_MAC
+    if constexpr (K0 != 0u || K1 != 0u) {
+        uint32_t lo, up;
+        asm volatile("v_mov_b32 %0, %2\\n\\tv_mov_b32 %1, %3" : "=v"(lo), "=v"(up) : "i"(K0), "i"(K1));
+        return (uint64_t)lo | ((uint64_t)up << 32);
+    }
+#endif
+    return (uint64_t)K0 | ((uint64_t)K1 << 32);
+}
+"""
+
+
 def main():
     parts = ["// GENERATED by tools/gen_u256_cols.py — do not edit.\n"
-             "// Product-scanning columns for mul256/sqr256 (see the generator's docstring).\n"
+             "// Product-scanning columns for mul256/sqr256 and the truncated multiply-adds built from\n"
+             "// them (see the generator's docstrings).\n"
              "#pragma once\nnamespace pf {\n#ifndef PF_HOST_MAC\n"]
     for n in range(1, 7):
         parts.append(carry_col(n))
@@ -80,7 +131,20 @@ def main():
         parts.append(host_col(n, True))
     for n in range(1, 9):
         parts.append(host_col(n, False))
-    parts.append("#endif\n}  // namespace pf\n")
+    parts.append("#endif\n")
+    parts.append(ACC_CONST)
+    shapes = [(L, LY) for L in range(1, 8) for LY in (L - 1, L) if LY >= 1]
+    for L, LY in shapes:
+        parts.append(tmulk(L, LY))
+    disp = ["// x * y + k mod 2^(32 L); K0, K1 are k[0], k[1] again, as constants\n"
+            "template <int L, int LY, uint32_t K0, uint32_t K1>\n"
+            "PF_INL void tmulk(const uint32_t* x, const uint32_t* y, const uint32_t* k, uint32_t* r) {\n"
+            "    static_assert(L >= 1 && L <= 7 && (LY == L || LY == L - 1) && LY >= 1, \"shape\");"]
+    for L, LY in shapes:
+        disp.append(f"    if constexpr (L == {L} && LY == {LY}) tmulk_{L}_{LY}<K0, K1>(x, y, k, r);")
+    disp.append("}\n")
+    parts.append("\n".join(disp))
+    parts.append("}  // namespace pf\n")
     open(OUT, "w").write("\n".join(parts))
     print(OUT)
 

@@ -503,7 +503,8 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #define PF_DO_ASSERT(v)                                                                       \
     do {                                                                                      \
         root &= (v);                                                                          \
-        if ((flags & PF_FLAG_SHORTCIRCUIT) && __ballot(root & (uint32_t)active) == 0ull) {   \
+        if ((flags & PF_FLAG_SHORTCIRCUIT) &&                                                 \
+            pf::wave_none(pf::wave_mask(root != 0u) & pf::wave_mask(active))) {               \
             In = make_uint4(PF_U_END << 21, 0u, 0u, 0u);                                      \
             sc = 1u;                                                                          \
         }                                                                                     \
@@ -643,10 +644,10 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 u256 q, rr;
 #ifdef PF_PROFILE_UNITS
                 {
-                    const uint32_t bz = pf::iszero256(ub);
-                    pbucket = !pf::wave_any((bz ^ 1u) & (pf::ult256(ua, ub) ^ 1u)) ? 11u
-                            : !pf::wave_any((ub.l[1] | ub.l[2] | ub.l[3] | ub.l[4] | ub.l[5] | ub.l[6] | ub.l[7]) != 0u) ? 12u
-                            : !pf::wave_any((bz ^ 1u) & (uint32_t)(pf::clz256(ub) > pf::clz256(ua) + 31u)) ? 13u : 14u;
+                    const uint64_t m_bz = pf::wave_mask(pf::iszero256(ub) != 0u);
+                    pbucket = pf::wave_none(pf::wave_mask(true) & ~(pf::wave_mask_ult256(ua, ub) | m_bz)) ? 11u
+                            : pf::wave_none(pf::wave_mask((ub.l[1] | ub.l[2] | ub.l[3] | ub.l[4] | ub.l[5] | ub.l[6] | ub.l[7]) != 0u)) ? 12u
+                            : pf::wave_none(pf::wave_mask(pf::clz256(ub) > pf::clz256(ua) + 31u) & ~m_bz) ? 13u : 14u;
                 }
 #endif
                 pf::udivrem256(ua, ub, &q, &rr);
@@ -905,9 +906,9 @@ PF_INL void search_item(const SetCtx& S, uint32_t set, uint32_t begin, uint32_t 
         uint64_t lane_ops = 0;
         uint32_t sat = run_program<MODE_GEN, NREG>(S, cand, active, flags, nullptr, 0u, exp_tbl, &complete,
                                              &lane_ops, &prof);
-        const uint64_t m_act = __ballot(active);
-        const uint64_t m_sat = __ballot((uint32_t)active & sat);
-        const uint64_t m_full = __ballot((uint32_t)active & complete);
+        const uint64_t m_act = pf::wave_mask(active);
+        const uint64_t m_sat = m_act & pf::wave_mask(sat != 0u);
+        const uint64_t m_full = m_act & pf::wave_mask(complete != 0u);
         decided += __popcll(m_act);
         evals_full += __popcll(m_full);
         ops += lane_ops * (uint64_t)__popcll(m_act);

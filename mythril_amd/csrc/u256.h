@@ -133,6 +133,17 @@ PF_INL uint32_t lane_mask(uint32_t c) {
     return m;
 }
 
+// A zero the optimiser cannot see through: the 9th limb of the divider's remainder, which a
+// borrow chain runs into.  As a literal 0 the chain's last step is folded into a negation
+// and a separate subtraction of the borrow, made a 0/1 lane value first.
+PF_INL uint32_t zero_limb() {
+    uint32_t z = 0u;
+#ifndef PF_HOST_MAC
+    asm("" : "+v"(z));
+#endif
+    return z;
+}
+
 PF_INL u256 sel256(uint32_t c, const u256& a, const u256& b) {
     const uint32_t m = lane_mask(c);
     u256 r;
@@ -148,11 +159,67 @@ PF_INL uint32_t wave_max_u32(uint32_t v) {
     for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
     return __builtin_amdgcn_readfirstlane(v);
 }
-PF_INL bool wave_any(bool p) { return __ballot(p) != 0ull; }
+// The wave's lane mask of one direct compare (`x != 0u`, `d >= 1.0`, a carry-out `!= 0u`):
+// the compare writes the mask into an SGPR pair and that pair is the result.  Conditions are
+// combined as masks, with & | ~ in scalar code, never as 0/1 lane values ahead of the ballot:
+// a ballot of `(uint32_t)(x >= y) & (skip ^ 1u)` makes the backend turn each mask into a 0/1
+// VGPR (v_cndmask_b32), and them, and compare the result with zero again — two to four VALU
+// instructions per test that the scalar form does not have.
+PF_INL uint64_t wave_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 #else
 PF_INL uint32_t wave_max_u32(uint32_t v) { return v; }
-PF_INL bool wave_any(bool p) { return p; }
+PF_INL uint64_t wave_mask(bool p) { return p ? 1ull : 0ull; }  // a wave is one lane: bit 0
 #endif
+// wave-uniform tests of (scalar combinations of) lane masks; `m & ~n` is the only use of ~, so
+// the host's one-bit masks need no trimming
+PF_INL bool wave_any(uint64_t m) { return m != 0ull; }
+PF_INL bool wave_none(uint64_t m) { return m == 0ull; }
+
+// The wave's mask of a < b: the borrow chain with its last step's carry-out written to an SGPR
+// pair, which the chain's carry flag as a C value never is — ballot(ult256(a, b) != 0u) has no
+// compare to take the mask from, and hipcc then replaces the eight-step chain by sixteen limb
+// compares and as many scalar and/ors.  gfx950 wants two wait states between a VALU writing
+// vcc and a VALU reading it as carry-in; inside an asm block they are ours to place.
+PF_INL uint64_t wave_mask_ult256(const u256& a, const u256& b) {
+#ifndef PF_HOST_MAC
+    uint64_t m;
+    uint32_t t;
+    asm("v_sub_co_u32 %1, vcc, %2, %10\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %3, %11, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %4, %12, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %5, %13, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %6, %14, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %7, %15, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %8, %16, vcc\n\ts_nop 1\n\t"
+        "v_subb_co_u32 %1, %0, %9, %17, vcc"
+        : "=s"(m), "=&v"(t)
+        : "v"(a.l[0]), "v"(a.l[1]), "v"(a.l[2]), "v"(a.l[3]), "v"(a.l[4]), "v"(a.l[5]), "v"(a.l[6]),
+          "v"(a.l[7]), "v"(b.l[0]), "v"(b.l[1]), "v"(b.l[2]), "v"(b.l[3]), "v"(b.l[4]), "v"(b.l[5]),
+          "v"(b.l[6]), "v"(b.l[7])
+        : "vcc");
+    return m;
+#else
+    return wave_mask(ult256(a, b) != 0u);
+#endif
+}
+
+// (uint32_t)min(x, 2^32 - 1) for a FINITE, NON-NEGATIVE x, truncated: one v_cvt_u32_f64, which
+// saturates by itself (x >= 2^32 and +inf give 0xFFFFFFFF), where the C conversion is undefined
+// out of range and so needed an fmin in front — and fmin brought a canonicalising v_max_f64 with
+// its v_min_f64, two f64-rate instructions per digit.  The precondition is the host form's: for
+// a negative x both give 0, but the hardware converts NaN to 0 and fmin(NaN, c) is c.  It holds
+// at all three sites in udivrem256: every argument is fma(n, r, bias) with bias = 2^-12 > 0,
+// n a Horner sum of uint32 limbs (finite, >= 0, < 2^289) and r the Newton reciprocal of a
+// double in [1, 2^256) (finite, > 0), so the fma is finite and positive.
+PF_INL uint32_t sat_u32(double x) {
+#ifndef PF_HOST_MAC
+    uint32_t r;
+    asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return (uint32_t)fmin(x, 4294967295.0);
+#endif
+}
 
 // ---- products ---------------------------------------------------------------------
 // Product scanning (column by column) with a 96-bit column accumulator (acc, hi): every
@@ -340,10 +407,13 @@ PF_INL double to_f64(const u256& a) {
 #define PF_DIV_BIAS 0x1p-12
 PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
     const uint32_t bz = iszero256(b);
+    // the lanes that divide by zero, as a mask: every wave-uniform test below leaves them out
+    // with one scalar and-not (bz itself stays a lane value for the final selects)
+    const uint64_t m_bz = wave_mask(bz != 0u);
     // quotient 0 (a < b) or division by zero in every lane of the wave: no digit to
     // produce (a quarter of the divisions of the config-3 DAGs)
 #ifndef PF_DIV_FORCE_GENERAL  // host fuzzing of the general path only (tools/u256_fuzz.py)
-    if (!wave_any((bz ^ 1u) & (ult256(a, b) ^ 1u))) {
+    if (wave_none(wave_mask(true) & ~(wave_mask_ult256(a, b) | m_bz))) {
         *q = sel256(bz, ones256(), zero256());
         *r = a;
         return;
@@ -351,7 +421,7 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
     // every lane's divisor fits one limb: short division, one 64/32 step per quotient digit
     // (an f64 estimate off by at most one, fixed exactly) instead of Knuth D's 8-limb
     // multiply-subtract per digit — these waves are the ones with 8-digit quotients
-    if (!wave_any((b.l[1] | b.l[2] | b.l[3] | b.l[4] | b.l[5] | b.l[6] | b.l[7]) != 0u)) {
+    if (wave_none(wave_mask((b.l[1] | b.l[2] | b.l[3] | b.l[4] | b.l[5] | b.l[6] | b.l[7]) != 0u))) {
         const uint32_t d = bz ? 1u : b.l[0];
         const double rd = rcp_f64((double)d);
         uint32_t rem = 0;
@@ -363,7 +433,7 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
             // estimate biased up by 2^-12 (relative error < 2^-50, the digit < 2^32): never
             // below the true digit, at most one above it, so one downward correction (a mask,
             // no per-lane branch)
-            uint32_t qj = (uint32_t)fmin(fma(dn, rd, 0x1p-12), 4294967295.0);
+            uint32_t qj = sat_u32(fma(dn, rd, 0x1p-12));
             int64_t rr = (int64_t)(num - (uint64_t)qj * d);
             const uint32_t lo = (uint32_t)(rr < 0);
             qj -= lo;
@@ -391,8 +461,8 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
     // negative remainder and is fixed by one add-back under a wave-uniform branch that
     // almost never runs — no normalisation shifts, no digit loop, no upward correction
     const double qest = fma(to_f64(a), rcp, PF_DIV_BIAS);
-    if (!wave_any((bz ^ 1u) & (uint32_t)(qest >= 4294967294.0))) {
-        uint32_t qh = (uint32_t)fmin(qest, 4294967295.0);
+    if (wave_none(wave_mask(qest >= 4294967294.0) & ~m_bz)) {
+        uint32_t qh = sat_u32(qest);
         // p = qh * b over 9 limbs, rem = a - p (borrow = rem negative)
         u256 R, Q = zero256();
         uint32_t carry = 0, bw = 0;
@@ -404,8 +474,14 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
             R.l[i] = __builtin_subc(a.l[i], (uint32_t)p, bw, &bo);
             bw = bo;
         }
-        const uint32_t neg = ((carry != 0u) | bw) & (bz ^ 1u);  // a < qh * b (9th limb too)
-        if (wave_any(neg)) {  // over-estimate: add b back once, qh - 1
+        // a < qh * b: the 9th limb of a - qh * b, 0 - carry - borrow, is non-zero — all ones,
+        // as qh is at most one too large and so a - qh * b >= -b > -2^256 — and 0 otherwise
+        // (a - qh * b <= a < 2^256; b = 0 lanes have p = 0).  One direct compare for the
+        // wave's test, where the chain's carry-out itself has no compare to ballot
+        uint32_t bo8;
+        const uint32_t r8 = __builtin_subc(zero_limb(), carry, bw, &bo8);
+        if (wave_any(wave_mask(r8 != 0u))) {  // over-estimate: add b back once, qh - 1
+            const uint32_t neg = (uint32_t)(r8 != 0u);
             const uint32_t m = lane_mask(neg);
             uint32_t c = 0;
 #pragma unroll
@@ -418,7 +494,7 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
         }
         Q.l[0] = qh;
         *q = sel256(bz, ones256(), Q);
-        *r = sel256(bz, a, R);
+        *r = R;  // b = 0 lanes: p = 0 and no add-back, so R = a already
         return;
     }
 #endif
@@ -438,8 +514,8 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
     uint32_t u[9];
 #pragma unroll
     for (int i = 0; i < 8; i++) u[i] = a.l[i];
-    u[8] = 0u;
     u256 Q = zero256();
+    u[8] = zero_limb();  // the 9th limb: 0 between digits (below), its register kept through them
     uint32_t sfx[9];  // sfx[k] = b.l[k] | .. | b.l[7]: b * 2^32j exceeds 9 limbs iff sfx[9-j] != 0
     sfx[8] = 0u;
 #pragma unroll
@@ -447,14 +523,18 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
 #pragma unroll
     for (int j = 7; j >= 0; j--) {
         const uint32_t bhigh = j >= 2 ? sfx[9 - j] : 0u;  // then q_j = 0
-        double dr = 0.0;
+        // 0 <= rem <= a < 2^256 between digits (a digit's subtraction leaves it non-negative,
+        // after the add-back if need be), so the 9th limb is a known zero here and the Horner
+        // sum starts at limb 7
+        double dr = (double)u[7];
 #pragma unroll
-        for (int i = 8; i >= j; i--) dr = fma(dr, 4294967296.0, (double)u[i]);
+        for (int i = 6; i >= j; i--) dr = fma(dr, 4294967296.0, (double)u[i]);
         // dr holds rem / 2^32j (its limbs below j only add a fraction < 1 ulp of a digit)
         const double qe = fma(dr, rcp, PF_DIV_BIAS);
+        // m_bz and the bhigh masks do not change across the digits: formed once
+        if (wave_none(wave_mask(qe >= 1.0) & ~(m_bz | wave_mask(bhigh != 0u)))) continue;  // digit 0 in every lane
         const uint32_t skip = bz | (uint32_t)(bhigh != 0u);
-        if (!wave_any((uint32_t)(qe >= 1.0) & (skip ^ 1u))) continue;  // digit 0 in every lane
-        uint32_t q = (uint32_t)fmin(qe, 4294967295.0) & ~lane_mask(skip);
+        uint32_t q = sat_u32(qe) & ~lane_mask(skip);
         // u[j .. 8] -= q * b
         uint64_t carry = 0;
         uint32_t borrow = 0;
@@ -466,9 +546,17 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
             u[j + i] = __builtin_subc(u[j + i], (uint32_t)p, borrow, &bo);
             borrow = bo;
         }
-        if (wave_any(borrow != 0u)) {  // over-estimate: add b * 2^32j back once
-            const uint32_t m = 0u - borrow;
-            q -= borrow;
+        // the borrow out of the chain is a carry flag, with no compare to ballot; the 9th limb
+        // is one: rem - q * b * 2^32j is below 2^256 when non-negative (limb 8 = 0) and, q
+        // being at most one too large, above -b * 2^32j > -2^257 when negative (limb 8 all
+        // ones) — q >= 1 needs b * 2^32j <= rem / (1 - 2^-12) < 2^257
+        if (wave_any(wave_mask(u[8] != 0u))) {  // over-estimate: add b * 2^32j back once
+            // = borrow, as a lane value only here; the add-back runs through limb 8 too, which
+            // puts its zero back (resetting it from a register per digit costs 2 VGPRs at
+            // the search kernels' peak)
+            const uint32_t neg = (uint32_t)(u[8] != 0u);
+            const uint32_t m = 0u - neg;
+            q -= neg;
             uint32_t c = 0;
 #pragma unroll
             for (int i = 0; i + j <= 8; i++) {
@@ -483,7 +571,9 @@ PF_INL void udivrem256(const u256& a, const u256& b, u256* q, u256* r) {
 #pragma unroll
     for (int i = 0; i < 8; i++) R.l[i] = u[i];
     *q = sel256(bz, ones256(), Q);
-    *r = sel256(bz, a, R);
+    // b = 0 lanes: every digit was masked to 0, so u is still a — no select, and a's
+    // registers are u's (no copy kept for one)
+    *r = R;
 }
 
 // base^e mod 2^256, left-to-right over 3-bit exponent digits (fixed window): one square per
@@ -873,7 +963,7 @@ PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t s
     u256 n = shr256(e, (uint32_t)M, 0u);
 #pragma unroll
     for (int i = 0; i < 8; i++) n.l[i] = i < TL - 1 ? n.l[i] : (i == TL - 1 ? n.l[i] & TM : 0u);
-    if (wave_any(odd & (iszero256(n) ^ 1u))) {
+    if (wave_any(wave_mask(odd != 0u) & ~wave_mask(iszero256(n) != 0u))) {
         // b^e0 waits in the LDS table's entry 1 (base^1, no longer needed) while the t
         // recurrence and the Horner chain run: 8 VGPRs fewer at their peak
         tbl_put(tbl, stride, 1u, r);

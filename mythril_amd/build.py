@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpathfeas.so")
-SOURCES = ["pathfeas.hip", "pf_eval.hip", "pf_keccak.hip", "pf_fold.h", "u256.h", "u256_cols.h",
+SOURCES = ["pathfeas.hip", "pf_eval.hip", "pf_keccak.hip", "pf_fold.h", "pf_hostint.h", "u256.h", "u256_cols.h",
            os.path.join("..", "..", "include", "pathfeas.h"),
            os.path.join("..", "..", "include", "pf_bytecode.h")]
 
@@ -30,7 +30,7 @@ def _stale() -> bool:
 
 
 LOWER_OUT = os.path.join(HERE, "libpflower.so")
-LOWER_SOURCES = ["pf_lower.cpp", "pf_seed.cpp", "pf_terms.cpp", "pf_recheck.cpp", "pf_pool.h", os.path.join("..", "..", "include", "pf_lower.h"),
+LOWER_SOURCES = ["pf_lower.cpp", "pf_seed.cpp", "pf_terms.cpp", "pf_recheck.cpp", "pf_hostint.h", "pf_pool.h", os.path.join("..", "..", "include", "pf_lower.h"),
                  os.path.join("..", "..", "include", "pf_bytecode.h")]
 
 

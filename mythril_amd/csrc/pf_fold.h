@@ -36,8 +36,8 @@
  * Every rule holds at every width 1..256 and under the total-division conventions of
  * include/pf_bytecode.h.  A rule is applied only where the operands fit the instruction's
  * width (values are kept zero-extended): M(w) below is the all-ones value of that width.
- * The 256-bit arithmetic is the fixed-width form of pf_recheck.cpp's evaluator (same
- * algorithms: schoolbook product, restoring division, square-and-multiply).
+ * What an instruction is on constants is pf_hostint.h's eval_op, the evaluator the hint solver
+ * shares; constants are its 256-bit integers, converted where they meet a pool's 8 x u32.
  */
 #ifndef PF_FOLD_H
 #define PF_FOLD_H
@@ -48,213 +48,24 @@
 #include <vector>
 
 #include "../../include/pf_bytecode.h"
+#include "pf_hostint.h"
 
 namespace pf_fold {
 
-// ---- 256-bit host arithmetic (little-endian limbs) -------------------------------------
-struct U {
-    uint32_t l[8];
-};
+using pf_host::bitlen;
+using pf_host::eval_op;
+using pf_host::lt;
+using pf_host::mask;
+using pf_host::mw;
+using pf_host::U;
 
-inline U uzero() {
-    U r;
-    memset(r.l, 0, sizeof r.l);
-    return r;
-}
-inline U usmall(uint32_t v) {
-    U r = uzero();
-    r.l[0] = v;
-    return r;
-}
-inline U umask(U a, uint32_t w) {
-    for (uint32_t j = 0; j < 8; j++) {
-        const uint32_t lo = 32u * j;
-        a.l[j] &= w >= lo + 32u ? 0xffffffffu : (w > lo ? (1u << (w - lo)) - 1u : 0u);
-    }
-    return a;
-}
-inline U uones(uint32_t w) {
-    U r;
-    memset(r.l, 0xff, sizeof r.l);
-    return umask(r, w);
-}
-inline bool uis0(const U& a) {
-    uint32_t x = 0;
-    for (int j = 0; j < 8; j++) x |= a.l[j];
-    return x == 0;
-}
-inline bool ueq(const U& a, const U& b) { return memcmp(a.l, b.l, sizeof a.l) == 0; }
-inline bool uis1(const U& a) { return ueq(a, usmall(1)); }
-inline int ucmp(const U& a, const U& b) {
-    for (int j = 7; j >= 0; j--)
-        if (a.l[j] != b.l[j]) return a.l[j] < b.l[j] ? -1 : 1;
-    return 0;
-}
-inline bool ubit(const U& a, uint32_t i) { return i < 256u && ((a.l[i / 32] >> (i % 32)) & 1u); }
-inline uint32_t ubitlen(const U& a) {
-    for (int j = 7; j >= 0; j--)
-        if (a.l[j]) return 32u * (uint32_t)j + 32u - (uint32_t)__builtin_clz(a.l[j]);
-    return 0;
-}
-inline U uadd(const U& a, const U& b, uint32_t* carry = nullptr) {
-    U r;
-    uint64_t c = 0;
-    for (int j = 0; j < 8; j++) {
-        c += (uint64_t)a.l[j] + b.l[j];
-        r.l[j] = (uint32_t)c;
-        c >>= 32;
-    }
-    if (carry) *carry = (uint32_t)c;
-    return r;
-}
-inline U unot(U a) {
-    for (int j = 0; j < 8; j++) a.l[j] = ~a.l[j];
-    return a;
-}
-inline U uneg(const U& a) { return uadd(unot(a), usmall(1)); }
-inline U usub(const U& a, const U& b) { return uadd(a, uneg(b)); }
-inline U umul(const U& a, const U& b) {
-    U r = uzero();
-    for (int i = 0; i < 8; i++) {
-        uint64_t c = 0;
-        for (int j = 0; i + j < 8; j++) {
-            c += (uint64_t)a.l[i] * b.l[j] + r.l[i + j];
-            r.l[i + j] = (uint32_t)c;
-            c >>= 32;
-        }
-    }
-    return r;
-}
-inline U ushl(const U& a, uint32_t s) {  // s < 256
-    U r = uzero();
-    const uint32_t q = s / 32, b = s % 32;
-    for (uint32_t i = q; i < 8; i++) {
-        uint32_t x = a.l[i - q] << b;
-        if (b && i > q) x |= a.l[i - q - 1] >> (32 - b);
-        r.l[i] = x;
-    }
-    return r;
-}
-inline U ulshr(const U& a, uint32_t s) {  // s < 256
-    U r = uzero();
-    const uint32_t q = s / 32, b = s % 32;
-    for (uint32_t i = 0; i + q < 8; i++) {
-        uint32_t x = a.l[i + q] >> b;
-        if (b && i + q + 1 < 8) x |= a.l[i + q + 1] << (32 - b);
-        r.l[i] = x;
-    }
-    return r;
-}
-inline void udivmod(const U& a, const U& b, U* q, U* r) {  // restoring division, b != 0
-    *q = uzero();
-    U R = uzero();
-    for (uint32_t i = ubitlen(a); i-- > 0;) {
-        const uint32_t top = R.l[7] >> 31;
-        R = ushl(R, 1);
-        R.l[0] |= (uint32_t)ubit(a, i);
-        if (top || ucmp(R, b) >= 0) {
-            R = usub(R, b);
-            q->l[i / 32] |= 1u << (i % 32);
-        }
-    }
-    *r = R;
-}
 // the value of a register shift amount when it is below w, else w
-inline uint32_t ushamt(const U& b, uint32_t w) {
-    for (int j = 1; j < 8; j++)
-        if (b.l[j]) return w;
-    return b.l[0] < w ? b.l[0] : w;
-}
-
-// A binary W opcode on operands below 2^w (SMT-LIB2 total functions, pf_bytecode.h)
-inline U eval_wbin(uint32_t op, const U& a, const U& b, uint32_t w) {
-    const bool sa = ubit(a, w - 1), sb = ubit(b, w - 1);
-    const U abs_a = sa ? umask(uneg(a), w) : a, abs_b = sb ? umask(uneg(b), w) : b;
-    U q, r;
-    switch (op) {
-        case PF_W_ADD: return umask(uadd(a, b), w);
-        case PF_W_SUB: return umask(usub(a, b), w);
-        case PF_W_MUL: return umask(umul(a, b), w);
-        case PF_W_UDIV:
-            if (uis0(b)) return uones(w);
-            udivmod(a, b, &q, &r);
-            return q;
-        case PF_W_UREM:
-            if (uis0(b)) return a;
-            udivmod(a, b, &q, &r);
-            return r;
-        case PF_W_SDIV:  // bvudiv on the magnitudes, negated when the signs differ (also b == 0)
-            if (uis0(abs_b)) q = uones(w);
-            else udivmod(abs_a, abs_b, &q, &r);
-            return sa != sb ? umask(uneg(q), w) : q;
-        case PF_W_SREM:  // sign of the dividend
-            if (uis0(abs_b)) r = abs_a;
-            else udivmod(abs_a, abs_b, &q, &r);
-            return sa ? umask(uneg(r), w) : r;
-        case PF_W_SMOD: {  // sign of the divisor
-            if (uis0(abs_b)) r = abs_a;
-            else udivmod(abs_a, abs_b, &q, &r);
-            if (uis0(r)) return r;
-            if (!sa && !sb) return r;
-            if (sa && !sb) return umask(uadd(uneg(r), b), w);
-            if (!sa && sb) return umask(uadd(r, b), w);
-            return umask(uneg(r), w);
-        }
-        case PF_W_AND:
-        case PF_W_OR:
-        case PF_W_XOR: {
-            U z;
-            for (int j = 0; j < 8; j++)
-                z.l[j] = op == PF_W_AND ? (a.l[j] & b.l[j]) : op == PF_W_OR ? (a.l[j] | b.l[j]) : (a.l[j] ^ b.l[j]);
-            return z;
-        }
-        case PF_W_SHL: {
-            const uint32_t s = ushamt(b, w);
-            return s >= w ? uzero() : umask(ushl(a, s), w);
-        }
-        case PF_W_LSHR: {
-            const uint32_t s = ushamt(b, w);
-            return s >= w ? uzero() : ulshr(a, s);
-        }
-        case PF_W_ASHR: {
-            const uint32_t s = ushamt(b, w);
-            if (s >= w) return sa ? uones(w) : uzero();
-            U z = ulshr(a, s);
-            if (sa)
-                for (uint32_t i = w - s; i < w; i++) z.l[i / 32] |= 1u << (i % 32);
-            return z;
-        }
-        default: {  // PF_W_EXP
-            U z = usmall(1), x = a;
-            const uint32_t nb = ubitlen(b);
-            for (uint32_t i = 0; i < nb; i++) {
-                if (ubit(b, i)) z = umul(z, x);
-                x = umul(x, x);
-            }
-            return umask(z, w);
-        }
-    }
-}
-
-// B_EQ .. B_SLE and B_UADD_NOOVF on operands below 2^w
-inline bool eval_cmp(uint32_t op, const U& a, const U& b, uint32_t w) {
-    const int c = ucmp(a, b);
-    switch (op) {
-        case PF_B_EQ: return c == 0;
-        case PF_B_ULT: return c < 0;
-        case PF_B_ULE: return c <= 0;
-        case PF_B_SLT:
-        case PF_B_SLE: {
-            const bool sa = ubit(a, w - 1), sb = ubit(b, w - 1);
-            if (sa != sb) return sa;
-            return op == PF_B_SLT ? c < 0 : c <= 0;
-        }
-        default: {  // PF_B_UADD_NOOVF
-            uint32_t carry;
-            const U s = uadd(a, b, &carry);
-            return !carry && ueq(s, umask(s, w));
-        }
-    }
+inline uint32_t ushamt(const U& b, uint32_t w) { return lt(b, U::of(w)) ? (uint32_t)b.w[0] : w; }
+// op(a, b) of an opcode the evaluator knows, which every caller below has checked
+inline U eval(uint32_t op, uint32_t w, uint32_t aux, const U& a, const U& b = U()) {
+    U r;
+    eval_op(op, w, aux, a, b, &r);
+    return r;
 }
 
 // ---- abstract values -------------------------------------------------------------------
@@ -334,10 +145,10 @@ inline uint32_t result_bound(uint32_t op, uint32_t pa, uint32_t pb, bool cb, con
         case PF_W_MUL: bd = pa + pb; break;
         case PF_W_UREM:
             bd = pa;
-            if (cb && !uis0(bv) && ubitlen(bv) < bd) bd = ubitlen(bv);
+            if (cb && !bv.zero() && bitlen(bv) < bd) bd = bitlen(bv);
             break;
         case PF_W_UDIV:
-            if (cb && !uis0(bv)) bd = pa >= ubitlen(bv) ? pa - ubitlen(bv) + 1u : 0u;
+            if (cb && !bv.zero()) bd = pa >= bitlen(bv) ? pa - bitlen(bv) + 1u : 0u;
             break;
         case PF_W_LSHR:
             if (cb) bd = pa > ushamt(bv, w) ? pa - ushamt(bv, w) : 0u;
@@ -353,14 +164,14 @@ inline uint32_t result_bound(uint32_t op, uint32_t pa, uint32_t pb, bool cb, con
 // B_EQ / B_ULT / B_ULE of an unknown value below 2^p against the constant c, the unknown on
 // the left (x op c) or on the right (c op x): 1 / 0 when the range decides it, else -1
 inline int range_cmp(uint32_t op, bool x_left, uint32_t p, const U& c, uint32_t w) {
-    const bool above = ubitlen(c) > p;  // c >= 2^p
+    const bool above = bitlen(c) > p;  // c >= 2^p
     if (op == PF_B_EQ) return above ? 0 : -1;
     if (x_left) {
-        if (op == PF_B_ULT) return uis0(c) ? 0 : above ? 1 : -1;
-        return above || ueq(c, uones(p)) ? 1 : -1;  // x <= c for c >= 2^p - 1
+        if (op == PF_B_ULT) return c.zero() ? 0 : above ? 1 : -1;
+        return above || c == mask(p) ? 1 : -1;  // x <= c for c >= 2^p - 1
     }
-    if (op == PF_B_ULE) return uis0(c) ? 1 : above ? 0 : -1;
-    return above || ueq(c, uones(w)) ? 0 : -1;  // c < x
+    if (op == PF_B_ULE) return c.zero() ? 1 : above ? 0 : -1;
+    return above || c == mask(w) ? 0 : -1;  // c < x
 }
 
 // The pass can reason about the program: it ends with its only END, every opcode is known,
@@ -416,20 +227,24 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
     while (hs < 2 * (size_t)n) hs <<= 1;
     T.heads.assign(hs, -1);
     T.n_vn = 0;
-    for (WV& x : T.W) x = WV{0, 256, T.fresh(), uzero()};
+    for (WV& x : T.W) x = WV{0, 256, T.fresh(), U()};
     for (BV& x : T.B) x = BV{0, 0, T.fresh()};
-    for (SV& x : T.S) x = SV{0, WV{0, 256, T.fresh(), uzero()}, BV{0, 0, T.fresh()}};
+    for (SV& x : T.S) x = SV{0, WV{0, 256, T.fresh(), U()}, BV{0, 0, T.fresh()}};
 
     auto pool_index = [&](const U& v) -> int64_t {
+        uint32_t l[8];
+        v.to32(l);
         for (uint32_t k = 0; pool && k < n_pool; k++)
-            if (memcmp(pool + 8 * (size_t)k, v.l, 32) == 0) return k;
+            if (memcmp(pool + 8 * (size_t)k, l, 32) == 0) return k;
         return -1;
     };
     const size_t extra0 = extra ? extra->size() : 0;  // this set's own constants start here
     auto own_index = [&](const U& v) -> uint32_t {
+        uint32_t l[8];
+        v.to32(l);
         for (size_t k = extra0; k < extra->size(); k += 8)
-            if (memcmp(extra->data() + k, v.l, 32) == 0) return n_pool + (uint32_t)((k - extra0) / 8);
-        extra->insert(extra->end(), v.l, v.l + 8);
+            if (memcmp(extra->data() + k, l, 32) == 0) return n_pool + (uint32_t)((k - extra0) / 8);
+        extra->insert(extra->end(), l, l + 8);
         return n_pool + (uint32_t)((extra->size() - extra0) / 8) - 1u;
     };
     constexpr uint8_t OWN_PENDING = 2;  // T.zero[i]: a W_CONST whose aux0 is an entry of T.own, no index yet
@@ -446,7 +261,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
 
         // a W result: constant val / the value of operand register src / a numbered unknown
         auto w_const = [&](const U& val, uint32_t operand) {
-            T.W[d] = WV{1, (uint16_t)ubitlen(val), T.fresh(), val};
+            T.W[d] = WV{1, (uint16_t)bitlen(val), T.fresh(), val};
             written |= (uint16_t)(1u << d);
             if (op == PF_W_CONST) return;
             const int64_t k = pool_index(val);
@@ -454,7 +269,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 I[0] = mk_w0(PF_W_CONST, w);
                 I[1] = d;
                 I[2] = (uint32_t)k;
-            } else if (uis0(val)) {
+            } else if (val.zero()) {
                 T.zero[i] = 1;
                 T.zreg[i] = (uint8_t)operand;
             } else if (extra) {  // its index once the backward walk has kept it
@@ -480,7 +295,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             written |= (uint16_t)(1u << d);
         };
         auto w_unknown = [&](uint32_t vn, uint32_t bound) {
-            T.W[d] = WV{0, (uint16_t)bound, vn, uzero()};
+            T.W[d] = WV{0, (uint16_t)bound, vn, U()};
             written |= (uint16_t)(1u << d);
         };
         auto b_const = [&](bool v) {
@@ -499,14 +314,14 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 continue;
             }
             const bool ca = A.konst, cb = B.konst, same = A.vn == B.vn;
-            const bool za = ca && uis0(A.v), zb = cb && uis0(B.v);
-            const bool oa = ca && uis1(A.v), ob = cb && uis1(B.v);
-            const bool ma = ca && ueq(A.v, uones(w)), mb = cb && ueq(B.v, uones(w));
+            const bool za = ca && A.v.zero(), zb = cb && B.v.zero();
+            const bool oa = ca && A.v == U::of(1), ob = cb && B.v == U::of(1);
+            const bool ma = ca && A.v == mask(w), mb = cb && B.v == mask(w);
             // the register of a constant operand: the cheaper writer to keep for a zero
             const uint32_t zr = cb ? b : a;
             enum { NONE, ZERO, ONE, ONES, CA, CB } r = NONE;
             if (ca && cb) {
-                w_const(eval_wbin(op, A.v, B.v, w), zr);
+                w_const(eval(op, w, 0, A.v, B.v), zr);
                 continue;
             }
             switch (op) {
@@ -527,11 +342,11 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 default: r = (zb || oa) ? ONE : ob ? CA : NONE; break;  // PF_W_EXP
             }
             if (r == NONE) {  // the range of the unknown operand against the constant one
-                const bool a_low = ca && ueq(umask(A.v, B.bound), uones(B.bound));
-                const bool b_low = cb && ueq(umask(B.v, A.bound), uones(A.bound));
+                const bool a_low = ca && mw(A.v, B.bound) == mask(B.bound);
+                const bool b_low = cb && mw(B.v, A.bound) == mask(A.bound);
                 switch (op) {
-                    case PF_W_UDIV: r = cb && ubitlen(B.v) > A.bound ? ZERO : NONE; break;
-                    case PF_W_UREM: r = cb && ubitlen(B.v) > A.bound ? CA : NONE; break;
+                    case PF_W_UDIV: r = cb && bitlen(B.v) > A.bound ? ZERO : NONE; break;
+                    case PF_W_UREM: r = cb && bitlen(B.v) > A.bound ? CA : NONE; break;
                     case PF_W_AND: r = b_low ? CA : a_low ? CB : NONE; break;
                     case PF_W_LSHR: r = cb && ushamt(B.v, w) >= A.bound ? ZERO : NONE; break;
                     default: break;
@@ -540,9 +355,9 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             const uint32_t bd = r == NONE ? result_bound(op, A.bound, B.bound, cb, B.v, w) : w;
             if (r == NONE && bd == 0) r = ZERO;
             switch (r) {
-                case ZERO: w_const(uzero(), zr); break;
-                case ONE: w_const(usmall(1), zr); break;
-                case ONES: w_const(uones(w), zr); break;
+                case ZERO: w_const(U(), zr); break;
+                case ONE: w_const(U::of(1), zr); break;
+                case ONES: w_const(mask(w), zr); break;
                 case CA: w_copy(a); break;
                 case CB: w_copy(b); break;
                 default: w_unknown(T.number(opw, A.vn, B.vn, 0, 0), bd); break;
@@ -560,7 +375,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 if ((A.konst && A.bound <= 1) || (B.konst && B.bound <= 1)) b_const(true);
                 else b_unknown(T.number(opw, A.vn, B.vn, 0, 0));
             } else if (A.konst && B.konst) {
-                b_const(eval_cmp(op, A.v, B.v, w));
+                b_const(!eval(op, w, 0, A.v, B.v).zero());
             } else if (same && op != PF_B_UADD_NOOVF) {
                 b_const(op == PF_B_EQ || op == PF_B_ULE || op == PF_B_SLE);
             } else {
@@ -579,9 +394,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
         switch (op) {
             case PF_W_CONST:
                 if (pool && aux0 < n_pool) {
-                    U v;
-                    memcpy(v.l, pool + 8 * (size_t)aux0, 32);
-                    w_const(umask(v, w), 0xff);
+                    w_const(mw(U::from32(pool + 8 * (size_t)aux0), w), 0xff);
                 } else {
                     w_unknown(T.number(opw, 0, 0, 0, aux0), w);
                 }
@@ -590,7 +403,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             case PF_W_MOV: {
                 const WV A = T.W[a];
                 if (A.bound <= w) w_copy(a);
-                else if (A.konst) w_const(umask(A.v, w), a);
+                else if (A.konst) w_const(mw(A.v, w), a);
                 else w_unknown(T.number(opw, A.vn, 0, 0, 0), w);
                 break;
             }
@@ -598,24 +411,22 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             case PF_W_NEG: {
                 const WV A = T.W[a];
                 if (A.bound > w) w_unknown(T.fresh(), 256);
-                else if (A.konst) w_const(umask(op == PF_W_NOT ? unot(A.v) : uneg(A.v), w), a);
+                else if (A.konst) w_const(eval(op, w, 0, A.v), a);
                 else w_unknown(T.number(opw, A.vn, 0, 0, 0), w);
                 break;
             }
             case PF_W_EXTRACT: {
                 const WV A = T.W[a];
                 const uint32_t bd = A.bound > aux0 ? A.bound - aux0 : 0u;
-                if (A.konst) w_const(umask(ulshr(A.v, aux0), w), a);
-                else if (bd == 0) w_const(uzero(), a);
+                if (A.konst) w_const(eval(op, w, aux0, A.v), a);
+                else if (bd == 0) w_const(U(), a);
                 else w_unknown(T.number(opw, A.vn, 0, 0, aux0), bd < w ? bd : w);
                 break;
             }
             case PF_W_CONCAT: {
                 const WV A = T.W[a], B = T.W[b];
                 if (A.konst && B.konst && B.bound <= aux0) {
-                    U v = ushl(A.v, aux0);
-                    for (int j = 0; j < 8; j++) v.l[j] |= B.v.l[j];
-                    w_const(umask(v, w), b);
+                    w_const(eval(op, w, aux0, A.v, B.v), b);
                 } else {
                     w_unknown(T.number(opw, A.vn, B.vn, 0, aux0), w);
                 }
@@ -624,10 +435,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             case PF_W_SEXT: {
                 const WV A = T.W[a];
                 if (A.konst && aux0 >= 1 && aux0 <= w && A.bound <= aux0) {
-                    U v = A.v;
-                    if (ubit(v, aux0 - 1))
-                        for (uint32_t k = aux0; k < w; k++) v.l[k / 32] |= 1u << (k % 32);
-                    w_const(v, a);
+                    w_const(eval(op, w, aux0, A.v), a);
                 } else {
                     w_unknown(T.number(opw, A.vn, 0, 0, aux0), w);
                 }
@@ -639,7 +447,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 if (A.bound > w || B.bound > w) w_unknown(T.fresh(), 256);
                 else if (C.konst) w_copy(C.v ? a : b);
                 else if (A.vn == B.vn) w_copy(a);
-                else if (A.konst && B.konst && ueq(A.v, B.v)) w_const(A.v, a);
+                else if (A.konst && B.konst && A.v == B.v) w_const(A.v, a);
                 else w_unknown(T.number(opw, A.vn, B.vn, C.vn, 0), A.bound > B.bound ? A.bound : B.bound);
                 break;
             }
@@ -651,7 +459,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                     if (s.w.konst) w_const(s.w.v, 0xff);
                     else w_unknown(s.w.vn, s.w.bound);
                 } else if (!s.is_b && s.w.konst) {
-                    w_const(umask(s.w.v, w), 0xff);
+                    w_const(mw(s.w.v, w), 0xff);
                 } else {
                     w_unknown(T.fresh(), w);
                 }
@@ -694,12 +502,12 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
                 else b_unknown(T.number(opw, A.vn, B.vn, C.vn, 0));
                 break;
             }
-            case PF_B_SPILL: T.S[aux0] = SV{1, WV{0, 256, 0, uzero()}, T.B[a]}; break;
+            case PF_B_SPILL: T.S[aux0] = SV{1, WV{0, 256, 0, U()}, T.B[a]}; break;
             case PF_B_FILL: {
                 const SV s = T.S[aux0];
                 if (s.is_b && s.b.konst) b_const(s.b.v);
                 else if (s.is_b) T.B[d] = s.b;
-                else if (s.w.konst) b_const(s.w.v.l[0] & 1u);
+                else if (s.w.konst) b_const(s.w.v.w[0] & 1u);
                 else b_unknown(T.fresh());
                 break;
             }

@@ -8,7 +8,10 @@
 // base_n + 64 (H(x) mod 2^117), inverses by lookup among the set's applications, Power by
 // argument value, other UFs as keyed hashes (PF_W_HASH).  gpu_check runs it on every bucket
 // witness before trusting it (soundness: a GPU "sat" must satisfy the terms, not only the
-// program); tests/test_native_terms.py checks it against Witness.ev.  Host code, no HIP.
+// program); tests/test_native_terms.py checks it against Witness.ev.  Its arithmetic (V, below)
+// is its own on purpose: terms are up to 512 bits and wider, where pf_hostint.h's integers
+// stop at 256, and a re-check that shared the lowering's evaluator would share its mistakes.
+// Only the keyed hash and the CRC-32 that salts it come from that header.  Host code, no HIP.
 #include <algorithm>
 #include <initializer_list>
 #include <cstdint>
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "../../include/pf_lower.h"
+#include "pf_hostint.h"
 #include "pf_pool.h"
 
 namespace {
@@ -372,35 +376,12 @@ bool cmpop(uint32_t op, const V& a, const V& b, uint32_t w) {  // terms._CMP
     }
 }
 
-// ---- PF_W_HASH (include/pf_bytecode.h) -----------------------------------------------------
-void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int i = 0; i < 10; i++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
+// PF_W_HASH of a value of up to 256 bits (pf_hostint.h: the hash is data, not arithmetic)
 V uf_hash(const V& x8, uint32_t salt) {
     uint32_t xs[8];
     for (int i = 0; i < 8; i++) xs[i] = i < (int)x8.size() ? x8[i] : 0u;
-    uint32_t h[4] = {xs[0], xs[1], xs[2], xs[3]};
-    philox(h, salt, 0x5BD1E995u);
-    uint32_t g[4] = {xs[4] ^ h[0], xs[5] ^ h[1], xs[6] ^ h[2], xs[7] ^ h[3]};
-    philox(g, salt, 0x27D4EB2Fu);
-    return V{h[0], h[1], h[2], h[3], g[0], g[1], g[2], g[3]};
-}
-
-uint32_t crc32_str(const std::string& s) {
-    uint32_t c = 0xffffffffu;
-    for (unsigned char ch : s) {
-        c ^= ch;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-    }
-    return c ^ 0xffffffffu;
+    pf_host::uf_hash32(xs, salt, xs);
+    return V(xs, xs + 8);
 }
 
 // chunks of a w-bit value: 256-bit pieces, LSB first (interp._chunks)
@@ -462,7 +443,7 @@ struct Ev {
                 if (vcmp(c.first, vmask(x, n)) == 0) return vmask(c.second, 256);
         V h;
         bool first = true;
-        const uint32_t salt = crc32_str("keccak256_" + std::to_string(n));
+        const uint32_t salt = pf_host::crc32("keccak256_" + std::to_string(n));
         for (const V& c : chunks256(x, n)) {
             V in = first ? vmask(c, 256) : binop(PFLT_BVXOR, h, vmask(c, 256), 256);
             h = uf_hash(in, salt);
@@ -537,7 +518,7 @@ struct Ev {
         if (f == "Power" && tv.nargs == 2 && width(tv) == 256) return power(t, tv);
         V h;
         bool first = true;
-        const uint32_t salt = crc32_str(f);
+        const uint32_t salt = pf_host::crc32(f);
         for (uint32_t i = 0; i < tv.nargs; i++) {
             const pflt_term_view a = T(tv.args[i]);
             for (const V& c : chunks256(ev(tv.args[i]), width(a))) {

@@ -4,9 +4,10 @@
 // concat, extract, extensions, shifts and divisions by constants, logic, add / sub /
 // odd-constant mul, not, neg), the same ordered choices for ite / or / and / xor / compares
 // with the same snapshot-and-retry discipline, the same repair rounds — so the hint values
-// are identical (tests/test_native_seed.py).  Values are 256-bit (4 x u64 limbs); interval
-// bounds that can leave [0, 2^256) (c - 1, lo + c, 2^w - c, signed bounds) are 320-bit
-// two's-complement.  Host code, no HIP.
+// are identical (tests/test_native_seed.py).  Values are pf_hostint.h's 256-bit integers, and
+// a node's value under the hint model is that header's eval_op; interval bounds that can
+// leave [0, 2^256) (c - 1, lo + c, 2^w - c, signed bounds) are 320-bit two's-complement.
+// Host code, no HIP.
 #include <cstdint>
 #include <cstring>
 
@@ -15,207 +16,11 @@
 
 #include "../../include/pf_bytecode.h"
 #include "../../include/pf_lower.h"
+#include "pf_hostint.h"
 
 namespace {
 
-// ---- 256-bit unsigned --------------------------------------------------------------------
-struct U {
-    uint64_t w[4] = {0, 0, 0, 0};
-    static U from32(const uint32_t* p) {
-        U r;
-        for (int i = 0; i < 4; i++) r.w[i] = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
-        return r;
-    }
-    static U of(uint64_t v) {
-        U r;
-        r.w[0] = v;
-        return r;
-    }
-    void to32(uint32_t* p) const {
-        for (int i = 0; i < 4; i++) {
-            p[2 * i] = (uint32_t)w[i];
-            p[2 * i + 1] = (uint32_t)(w[i] >> 32);
-        }
-    }
-    bool zero() const { return !(w[0] | w[1] | w[2] | w[3]); }
-    bool operator==(const U& o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
-    bool operator!=(const U& o) const { return !(*this == o); }
-};
-
-int cmp(const U& a, const U& b) {
-    for (int i = 3; i >= 0; i--)
-        if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1;
-    return 0;
-}
-bool lt(const U& a, const U& b) { return cmp(a, b) < 0; }
-bool le(const U& a, const U& b) { return cmp(a, b) <= 0; }
-U uand(const U& a, const U& b) { U r; for (int i = 0; i < 4; i++) r.w[i] = a.w[i] & b.w[i]; return r; }
-U uor(const U& a, const U& b) { U r; for (int i = 0; i < 4; i++) r.w[i] = a.w[i] | b.w[i]; return r; }
-U uxor(const U& a, const U& b) { U r; for (int i = 0; i < 4; i++) r.w[i] = a.w[i] ^ b.w[i]; return r; }
-U unot(const U& a) { U r; for (int i = 0; i < 4; i++) r.w[i] = ~a.w[i]; return r; }
-U add(const U& a, const U& b, uint64_t* carry = nullptr) {
-    U r;
-    unsigned __int128 c = 0;
-    for (int i = 0; i < 4; i++) {
-        c += (unsigned __int128)a.w[i] + b.w[i];
-        r.w[i] = (uint64_t)c;
-        c >>= 64;
-    }
-    if (carry) *carry = (uint64_t)c;
-    return r;
-}
-U sub(const U& a, const U& b) {
-    U r;
-    uint64_t br = 0;
-    for (int i = 0; i < 4; i++) {
-        const uint64_t x = a.w[i], y = b.w[i];
-        const uint64_t d = x - y - br;
-        br = (x < y) || (x - y < br);
-        r.w[i] = d;
-    }
-    return r;
-}
-U neg(const U& a) { return sub(U(), a); }
-U shl(const U& a, unsigned k) {
-    U r;
-    if (k >= 256) return r;
-    const unsigned q = k / 64, s = k % 64;
-    for (int i = 3; i >= 0; i--) {
-        const int j = i - (int)q;
-        uint64_t v = 0;
-        if (j >= 0) {
-            v = a.w[j] << s;
-            if (s && j >= 1) v |= a.w[j - 1] >> (64 - s);
-        }
-        r.w[i] = v;
-    }
-    return r;
-}
-U shr(const U& a, unsigned k) {
-    U r;
-    if (k >= 256) return r;
-    const unsigned q = k / 64, s = k % 64;
-    for (int i = 0; i < 4; i++) {
-        const unsigned j = i + q;
-        uint64_t v = 0;
-        if (j < 4) {
-            v = a.w[j] >> s;
-            if (s && j + 1 < 4) v |= a.w[j + 1] << (64 - s);
-        }
-        r.w[i] = v;
-    }
-    return r;
-}
-U mask_slow(unsigned w) {
-    if (w >= 256) return unot(U());
-    return sub(shl(U::of(1), w), U::of(1));
-}
-struct MaskTable {
-    U m[257];
-    MaskTable() {
-        for (unsigned w = 0; w <= 256; w++) m[w] = mask_slow(w);
-    }
-};
-const U& mask(unsigned w) {  // 2^w - 1
-    static const MaskTable t;
-    return t.m[w >= 256 ? 256 : w];
-}
-U mw(const U& a, unsigned w) { return uand(a, mask(w)); }
-unsigned bitlen(const U& a) {
-    for (int i = 3; i >= 0; i--)
-        if (a.w[i]) return 64 * i + 64 - __builtin_clzll(a.w[i]);
-    return 0;
-}
-bool bit(const U& a, unsigned k) { return k < 256 && ((a.w[k / 64] >> (k % 64)) & 1u); }
-// full 512-bit product (lo, hi)
-void mul_full(const U& a, const U& b, U* lo, U* hi) {
-    uint64_t r[8] = {0};
-    for (int i = 0; i < 4; i++) {
-        unsigned __int128 c = 0;
-        for (int j = 0; j < 4; j++) {
-            c += (unsigned __int128)a.w[i] * b.w[j] + r[i + j];
-            r[i + j] = (uint64_t)c;
-            c >>= 64;
-        }
-        r[i + 4] = (uint64_t)c;
-    }
-    for (int i = 0; i < 4; i++) {
-        lo->w[i] = r[i];
-        hi->w[i] = r[i + 4];
-    }
-}
-U mul(const U& a, const U& b) {
-    U lo, hi;
-    mul_full(a, b, &lo, &hi);
-    return lo;
-}
-void divmod(const U& a, const U& b, U* q, U* r) {  // b != 0
-    if (lt(a, b)) {
-        *q = U();
-        *r = a;
-        return;
-    }
-    if (!(b.w[1] | b.w[2] | b.w[3])) {  // one-limb divisor: 128/64 steps
-        const uint64_t d = b.w[0];
-        U Q;
-        unsigned __int128 rem = 0;
-        for (int i = 3; i >= 0; i--) {
-            const unsigned __int128 cur = (rem << 64) | a.w[i];
-            Q.w[i] = (uint64_t)(cur / d);
-            rem = cur % d;
-        }
-        *q = Q;
-        *r = U::of((uint64_t)rem);
-        return;
-    }
-    // restoring division from the first quotient bit that can be set (the bits of a above
-    // it are below b)
-    const int k0 = (int)bitlen(a) - (int)bitlen(b);
-    U Q, R = shr(a, (unsigned)k0 + 1u);
-    for (int k = k0; k >= 0; k--) {
-        R = shl(R, 1);
-        if (bit(a, (unsigned)k)) R.w[0] |= 1;
-        if (!lt(R, b)) {
-            R = sub(R, b);
-            Q.w[k / 64] |= 1ull << (k % 64);
-        }
-    }
-    *q = Q;
-    *r = R;
-}
-U powmod(U a, const U& e, unsigned w) {  // a^e mod 2^w
-    U r = U::of(1);
-    const unsigned n = bitlen(e);
-    for (unsigned k = 0; k < n; k++) {
-        if (bit(e, k)) r = mul(r, a);
-        a = mul(a, a);
-    }
-    return mw(r, w);
-}
-bool negw(const U& a, unsigned w) { return w >= 1 && bit(a, w - 1); }
-U absw(const U& a, unsigned w) { return negw(a, w) ? mw(neg(a), w) : a; }
-
-uint32_t mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
-void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int i = 0; i < 10; i++) {
-        const uint64_t p0 = (uint64_t)PF_PHILOX_M0 * c[0], p1 = (uint64_t)PF_PHILOX_M1 * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1,
-                       n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += PF_PHILOX_W0;
-        k1 += PF_PHILOX_W1;
-    }
-}
-U uf_hash(const U& x, uint32_t salt) {  // PF_W_HASH
-    uint32_t xs[8];
-    x.to32(xs);
-    uint32_t h[4] = {xs[0], xs[1], xs[2], xs[3]};
-    philox(h, salt, PF_HASH_K1A);
-    uint32_t g[4] = {xs[4] ^ h[0], xs[5] ^ h[1], xs[6] ^ h[2], xs[7] ^ h[3]};
-    philox(g, salt, PF_HASH_K1B);
-    uint32_t o[8] = {h[0], h[1], h[2], h[3], g[0], g[1], g[2], g[3]};
-    return U::from32(o);
-}
+using namespace pf_host;  // U and its arithmetic, eval_op
 
 // ---- 320-bit two's complement for interval bounds ----------------------------------------
 struct S {
@@ -429,95 +234,19 @@ class Seeder {
             case PFL_K_CONST: return mw(pool[nd.aux], w);
             case PFL_K_BCONST: return B(nd.aux != 0);
             case PFL_K_BVAR: return B(value_of_var((int)nd.aux).w[0] & 1);
-            case PF_W_ADD: return mw(add(A(0), A(1)), w);
-            case PF_W_SUB: return mw(sub(A(0), A(1)), w);
-            case PF_W_MUL: return mw(mul(A(0), A(1)), w);
-            case PF_W_UDIV: {
-                if (A(1).zero()) return mask(w);
-                U q, r;
-                divmod(A(0), A(1), &q, &r);
-                return mw(q, w);
-            }
-            case PF_W_UREM: {
-                if (A(1).zero()) return mw(A(0), w);
-                U q, r;
-                divmod(A(0), A(1), &q, &r);
-                return mw(r, w);
-            }
-            case PF_W_SDIV: {
-                const bool na = negw(A(0), w), nb = negw(A(1), w);
-                if (A(1).zero()) return na ? U::of(1) : mask(w);
-                U q, r;
-                divmod(absw(A(0), w), absw(A(1), w), &q, &r);
-                return mw(na == nb ? q : neg(q), w);
-            }
-            case PF_W_SREM: {
-                if (A(1).zero()) return mw(A(0), w);
-                const bool na = negw(A(0), w);
-                U q, r;
-                divmod(absw(A(0), w), absw(A(1), w), &q, &r);
-                return mw(na ? neg(r) : r, w);
-            }
-            case PF_W_SMOD: {  // Python floor mod of the signed values: sign of the divisor
-                if (A(1).zero()) return mw(A(0), w);
-                const bool na = negw(A(0), w), nb = negw(A(1), w);
-                const U mb = absw(A(1), w);
-                U q, r;
-                divmod(absw(A(0), w), mb, &q, &r);
-                if (r.zero()) return U();
-                U res;
-                if (!na && !nb) res = r;
-                else if (na && !nb) res = sub(mb, r);
-                else if (!na && nb) res = neg(sub(mb, r));
-                else res = neg(r);
-                return mw(res, w);
-            }
-            case PF_W_AND: return mw(uand(A(0), A(1)), w);
-            case PF_W_OR: return mw(uor(A(0), A(1)), w);
-            case PF_W_XOR: return mw(uxor(A(0), A(1)), w);
-            case PF_W_SHL: return (lt(A(1), U::of(w))) ? mw(shl(A(0), (unsigned)A(1).w[0]), w) : U();
-            case PF_W_LSHR: return (lt(A(1), U::of(w))) ? mw(shr(A(0), (unsigned)A(1).w[0]), w) : U();
-            case PF_W_ASHR: {
-                const bool na = negw(A(0), w);
-                if (!lt(A(1), U::of(w))) return na ? mask(w) : U();
-                const unsigned s = (unsigned)A(1).w[0];
-                U r = shr(A(0), s);
-                if (na) r = uor(r, uand(mask(w), unot(mask(w - s))));
-                return mw(r, w);
-            }
-            case PF_W_EXP: return powmod(A(0), A(1), w);
-            case PF_W_NOT: return mw(unot(A(0)), w);
-            case PF_W_NEG: return mw(neg(A(0)), w);
-            case PF_W_MOV: return mw(A(0), w);
-            case PF_W_EXTRACT: return mw(shr(A(0), nd.aux), w);
-            case PF_W_CONCAT: return mw(uor(shl(A(0), nd.aux), A(1)), w);
-            case PF_W_SEXT: {
-                const U x = mw(A(0), nd.aux);
-                return mw(negw(x, nd.aux) ? sub(x, shl(U::of(1), nd.aux)) : x, w);
-            }
             case PF_W_ITE: return A(0).zero() ? A(2) : A(1);
-            case PF_W_HASH: return mw(uf_hash(A(0), nd.aux), w);
             case PF_B_AND: return B(!A(0).zero() && !A(1).zero());
             case PF_B_OR: return B(!A(0).zero() || !A(1).zero());
             case PF_B_XOR: return B(A(0).zero() != A(1).zero());
             case PF_B_NOT: return B(A(0).zero());
             case PF_B_ITE: return A(0).zero() ? A(2) : A(1);
-            case PF_B_EQ: return B(A(0) == A(1));
-            case PF_B_ULT: return B(lt(A(0), A(1)));
-            case PF_B_ULE: return B(le(A(0), A(1)));
-            case PF_B_SLT: return B(scmp(sgn(A(0), w), sgn(A(1), w)) < 0);
-            case PF_B_SLE: return B(scmp(sgn(A(0), w), sgn(A(1), w)) <= 0);
-            case PF_B_UADD_NOOVF: {
-                uint64_t c;
-                const U s = add(A(0), A(1), &c);
-                return B(!c && le(s, mask(w)));
+            default: {  // every function of one or two values: the shared evaluator
+                static const U none{};
+                U r;
+                if (!eval_op(k, w, nd.aux, nd.nargs > 0 ? A(0) : none, nd.nargs > 1 ? A(1) : none, &r))
+                    throw Conflict{};  // cannot evaluate: the caller's try absorbs it
+                return r;
             }
-            case PF_B_UMUL_NOOVF: {
-                U lo, hi;
-                mul_full(A(0), A(1), &lo, &hi);
-                return B(hi.zero() && le(lo, mask(w)));
-            }
-            default: throw Conflict{};  // cannot evaluate: the caller's try absorbs it
         }
     }
 

@@ -33,6 +33,7 @@
 
 #include "../../include/pf_bytecode.h"
 #include "../../include/pf_lower.h"
+#include "pf_hostint.h"
 #include "pf_pool.h"
 
 namespace {
@@ -120,38 +121,12 @@ C8 c8_small(uint64_t x, uint32_t w) {
 
 Big big_of(const C8& c) { return Big(c.l, c.l + 8); }
 
-// a * b mod 2^256 and b^e mod 2^256 (Power's concrete facts, pow(c1, c2, 1 << 256))
-C8 mul8(const C8& a, const C8& b) {
-    uint32_t r[8] = {0};
-    for (int i = 0; i < 8; i++) {
-        uint64_t c = 0;
-        for (int j = 0; i + j < 8; j++) {
-            c += (uint64_t)a.l[i] * b.l[j] + r[i + j];
-            r[i + j] = (uint32_t)c;
-            c >>= 32;
-        }
-    }
-    C8 o;
-    memcpy(o.l, r, sizeof(r));
-    return o;
-}
-
-C8 pow8(const C8& b, const C8& e) {
-    C8 r = c8_small(1, 256), x = b;
-    for (int i = 0; i < 256; i++) {
-        if ((e.l[i / 32] >> (i % 32)) & 1u) r = mul8(r, x);
-        x = mul8(x, x);
-    }
-    return r;
-}
-
-uint32_t crc32_of(const std::string& s) {  // zlib.crc32 (to_dag.salt_of)
-    uint32_t c = 0xffffffffu;
-    for (unsigned char ch : s) {
-        c ^= ch;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-    }
-    return c ^ 0xffffffffu;
+// to and from the integers that compute (pf_hostint.h)
+pf_host::U u_of(const C8& c) { return pf_host::U::from32(c.l); }
+C8 c8_of(const pf_host::U& u) {
+    C8 c;
+    u.to32(c.l);
+    return c;
 }
 
 // ---- the term store -------------------------------------------------------------------
@@ -1401,7 +1376,7 @@ struct Lowering {
         }
         if (r.name == "Power" && r.args.size() == 2 && width(t) == 256) return V(power(t));
         uf_apps.push_back(t);
-        const int32_t h = hash_args(r.args, crc32_of(r.name));
+        const int32_t h = hash_args(r.args, pf_host::crc32(r.name));
         return V(width(t) == 256 ? h : d.op(PF_W_EXTRACT, width(t), {h}, 0));
     }
 
@@ -1440,7 +1415,7 @@ struct Lowering {
         auto& apps = keccak_apps[n];
         for (const auto& a : apps)
             if (a.first == arg) return a.second;
-        const int32_t h = hash_args({arg}, crc32_of("keccak256_" + std::to_string(n)));
+        const int32_t h = hash_args({arg}, pf_host::crc32("keccak256_" + std::to_string(n)));
         int32_t val = h;
         auto sit = kspecs.find(n);
         if (sit != kspecs.end()) {
@@ -1503,7 +1478,8 @@ struct Lowering {
         int32_t val;
         const bool sym = !(T(bt).op == T_BV && T(et).op == T_BV);
         if (!sym) {
-            val = d.cnst(pow8(c8_of(T(bt).val, 256), c8_of(T(et).val, 256)), 256);
+            // pow(c1, c2, 1 << 256)
+            val = d.cnst(c8_of(pf_host::powmod(u_of(c8_of(T(bt).val, 256)), u_of(c8_of(T(et).val, 256)), 256)), 256);
         } else {
             const int32_t bn = node(bt), en = node(et);
             size_t nsym = 0;
@@ -1543,7 +1519,7 @@ struct Lowering {
             if (r.op == T_APPLY && r.name == "Power" && r.args.size() == 2 && T(r.args[0]).op == T_BV &&
                 T(r.args[1]).op == T_BV) {
                 const C8 c1 = c8_of(T(r.args[0]).val, 256), c2 = c8_of(T(r.args[1]).val, 256);
-                const C8 pv = pow8(c1, c2);
+                const C8 pv = c8_of(pf_host::powmod(u_of(c1), u_of(c2), 256));
                 bool found = false;
                 for (auto& f : power_facts)
                     if (f.first.first == c1 && f.first.second == c2) {

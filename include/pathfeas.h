@@ -126,6 +126,23 @@ int pf_check_batch_dev(uint64_t handle, uint64_t global_seed, uint32_t budget, u
 int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_ids,
                    const uint32_t* cand_ids, size_t n, uint32_t* values_out);
 
+/* Climb the sets set_ids[0 .. n) of a batch (include/pf_bytecode.h, climb contract): `rounds`
+ * scored searches of `per_round` candidates each, every round's best near miss the parent
+ * model of the next; the rounds run back to back on the batch's stream.  For sets the plain
+ * search found nothing for — a climb's witness is an assignment, not a (seed, index) of that
+ * search, hence values.
+ * status_out[i] = PF_CLIMB_NONE / PF_CLIMB_WITNESS / PF_CLIMB_CUT, score_out[i] = the score of
+ * the final assignment, round_out[i] = the round that generated it; values_out = the final
+ * assignments, n_vars(set) x 8 u32 per request, concatenated in request order (pf_materialize's
+ * layout).  A set id may appear once.  stats: evals_full = cands_decided = candidate
+ * evaluations over all rounds, n_sat = witnessed sets, kernel_ms over all rounds, timed_out as
+ * for pf_check_batch.  rounds == 0, per_round == 0, a set id out of range or repeated: error,
+ * nothing launched.                                                                        */
+int pf_climb_batch(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint32_t per_round,
+                   uint32_t timeout_ms, const uint32_t* set_ids, size_t n,
+                   uint32_t* status_out, uint32_t* score_out, uint32_t* round_out,
+                   uint32_t* values_out, pf_stats* stats);
+
 /* Evaluate set `set` on n_cand explicit assignments, SoA limbs [var][limb][cand].          */
 int pf_eval_assignments(uint64_t handle, uint32_t set, const uint32_t* soa, uint32_t n_cand,
                         uint8_t* sat_out);

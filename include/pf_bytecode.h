@@ -273,6 +273,48 @@ typedef struct pf_set_desc {
 #define PF_PHILOX_W0 0x9E3779B9u
 #define PF_PHILOX_W1 0xBB67AE85u
 
+/* ---- climb contract ------------------------------------------------------------- */
+/* A climb (pf_climb_batch) is a loop of ordinary searches under the generator contract above
+ * that learns from near misses: each round scores every candidate and the best one becomes the
+ * parent model of the next round, whose odd candidates and strategies 12, 13 are its
+ * few-variable and single-bit mutations.  Nothing in the generator contract changes.
+ *
+ * Score of a candidate on the set's device program (what pf_batch_create uploads and
+ * pf_device_batch returns): the sum over the program's assert sites — every PF_ASSERT and
+ * every B op carrying PF_I_ASSERT — of
+ *    PF_CLIMB_HOLDS                            the site holds
+ *    PF_CLIMB_NEAR - popcount(a ^ b)           it fails and is a PF_B_EQ carrying PF_I_ASSERT
+ *    PF_CLIMB_NEAR - bitlen(|a - b|)           it fails and is a PF_B_ULT, PF_B_ULE, PF_B_SLT or
+ *                                              PF_B_SLE carrying PF_I_ASSERT; a, b are the
+ *                                              zero-extended 256-bit register values taken as
+ *                                              unsigned (also for the signed compares), and
+ *                                              bitlen(0) = 0
+ *    0                                         any other failing site
+ * as a u32.  A failing site adds at most PF_CLIMB_NEAR < PF_CLIMB_HOLDS, so PF_CLIMB_HOLDS x
+ * sites is the score of a witness and of nothing else.  A scored run never short-circuits.
+ *
+ * Rounds.  Parameters: rounds R, per_round N, global seed G.  Round r = 0 .. R-1 generates
+ * candidates [0, N) with global seed
+ *    G_r = (G + (r + 1) * PF_CLIMB_SEED_MUL) mod 2^64
+ * (so no round repeats the plain search's candidates under G).  In round 0 the parents are the
+ * set's own (a variable without one has none); in round r >= 1 every variable's parent is its
+ * value in the current assignment A_r.  The round's best candidate is the one of highest score,
+ * ties to the smallest index; from round 1 on candidate 0 is left out (it is A_r itself).  It is
+ * adopted — A_{r+1} = its values, the current score = its score — when its score is >= the
+ * current score (a sideways move is a move); the current score before round 0 is 0, so round
+ * 0's best is always adopted.  Otherwise A_{r+1} = A_r.  A set stops at a witness
+ * (PF_CLIMB_WITNESS) or after R rounds (PF_CLIMB_NONE); a set the device deadline kept from
+ * evaluating a whole round stops as PF_CLIMB_CUT with the assignment and score it had.  The
+ * recorded round is the one that generated the returned assignment.                       */
+enum pf_climb_status {
+    PF_CLIMB_NONE = 0,
+    PF_CLIMB_WITNESS = 1,
+    PF_CLIMB_CUT = 2
+};
+#define PF_CLIMB_HOLDS 512u
+#define PF_CLIMB_NEAR 256u
+#define PF_CLIMB_SEED_MUL 0x9E3779B97F4A7C15ull
+
 /* flags for pf_check_batch */
 #define PF_FLAG_SHORTCIRCUIT 1u  /* stop a wave's set evaluation once all its lanes are false */
 #define PF_FLAG_EARLY_EXIT 2u    /* stop a set once any candidate satisfies it             */

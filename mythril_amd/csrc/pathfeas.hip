@@ -146,8 +146,17 @@ struct Batch {
                                     // has no variables
     uint32_t* d_scratch = nullptr;  // this batch's t0 (u64 [4]), queue heads and counter lines (pf_bytecode.h)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // climb (pf_climb_batch): per set, whether it runs the 16-register kernels and the assert
+    // sites of its device program; the climb block — working descriptors and schema (every
+    // variable parented), the two parent buffers, the per-set states — is allocated by the
+    // batch's first climb and lives as long as the batch
+    std::vector<uint8_t> h_wide;
+    std::vector<uint32_t> h_sites;
+    void* c_mem = nullptr;
+    size_t c_cap = 0;
     ~Batch() {  // the device block goes back to its device's pool first (release_batch)
         if (d_mem) hipFree(d_mem);
+        if (c_mem) hipFree(c_mem);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
     }
@@ -209,6 +218,10 @@ void release_batch(Dev* D, Batch* B) {
     if (D && B->d_mem) {
         pool_release(D, B->d_mem, B->mem_cap);
         B->d_mem = nullptr;
+    }
+    if (D && B->c_mem) {
+        pool_release(D, B->c_mem, B->c_cap);
+        B->c_mem = nullptr;
     }
     if (D) {
         std::lock_guard<std::mutex> pk(g_pool_mu);
@@ -1193,14 +1206,18 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     // (EXP ~7.1k, a division ~2.6k, MUL ~750, cheap ~650).  8-register sets
     // come first (their launch precedes the 16-register one's).
     std::vector<uint64_t> cost(n_sets, 0);
+    std::vector<uint32_t> sites(n_sets, 0);  // assert sites (the climb contract's witness score)
     for (size_t s = 0; s < n_sets; ++s) {
         const uint4* I = reinterpret_cast<const uint4*>(code) + descs[s].code_off;
         uint64_t c = 0;
+        uint32_t ns = 0;
         for (uint32_t i = 0; i < descs[s].n_ins; ++i) {
             const uint32_t op = I[i].x & 0xffu;
             c += op == PF_W_EXP ? 110u : op == PF_W_MUL ? 12u : pf_op_unit(op) == PF_U_DIV ? 40u : 10u;
+            ns += (uint32_t)(op == PF_ASSERT) | (uint32_t)((I[i].x & PF_I_ASSERT) != 0u);
         }
         cost[s] = c;
+        sites[s] = ns;
     }
     std::vector<uint32_t> order(n_sets);
     for (size_t s = 0; s < n_sets; ++s) order[s] = (uint32_t)s;
@@ -1274,6 +1291,8 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
             return d.parent_off != PF_NO_PARENT || d.n_vars == 0;
         });
         B->h_descs.assign(descs, descs + n_sets);
+        B->h_wide = wide;
+        B->h_sites = std::move(sites);
         B->d_mem = pool_acquire(Dv, total, &B->mem_cap);
         if (!B->d_mem) {
             delete B;
@@ -1486,6 +1505,152 @@ int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_id
     }
     // back to the pool (the stream is drained)
     pool_release(D, dm, cap);
+    return 0;
+}
+
+int pf_climb_batch(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint32_t per_round,
+                   uint32_t timeout_ms, const uint32_t* set_ids, size_t n, uint32_t* status_out,
+                   uint32_t* score_out, uint32_t* round_out, uint32_t* values_out, pf_stats* stats) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    if (!B) return fail("pf_climb_batch: null batch");
+    if (rounds == 0) return fail("pf_climb_batch: rounds must be at least 1");
+    if (per_round == 0) return fail("pf_climb_batch: per_round must be at least 1");
+    if (n && !set_ids) return fail("pf_climb_batch: null set_ids");
+    const size_t ns = B->n_sets;
+    {
+        std::vector<uint8_t> seen(ns, 0);
+        for (size_t i = 0; i < n; i++) {
+            if (set_ids[i] >= ns) return fail("pf_climb_batch: set %u out of range (%zu sets)", set_ids[i], ns);
+            if (seen[set_ids[i]]) return fail("pf_climb_batch: set %u requested twice", set_ids[i]);
+            seen[set_ids[i]] = 1;
+        }
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return 0;
+    const uint32_t groups = (uint32_t)(((uint64_t)per_round + 63u) / 64u);
+    if ((uint64_t)n * groups > 0xffffffffull) return fail("pf_climb_batch: %zu sets x %u groups is too many items", n, groups);
+    Dev* D = use_dev(B->device);
+    if (!D) return -1;
+    hipStream_t st = D->stream;
+    if (switch_stream(D, st)) return -1;
+
+    // the climb block: [working descs | working schema | parent buffers A, B | states | per set:
+    // first parent row, witness score | this call's set ids, 8-register sets first]
+    std::vector<uint32_t> wvoff(ns);
+    size_t n_wvars = 0;
+    for (size_t s = 0; s < ns; s++) {
+        wvoff[s] = (uint32_t)n_wvars;
+        n_wvars += B->h_descs[s].n_vars;
+    }
+    if (n_wvars > 0xffffffffull / 8) return fail("pf_climb_batch: %zu variables", n_wvars);
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_wd = 0, o_ws = o_wd + al(ns * sizeof(pf_set_desc)), o_p0 = o_ws + al(n_wvars * 16 + 16),
+                 o_p1 = o_p0 + al(n_wvars * 32 + 32), o_st = o_p1 + al(n_wvars * 32 + 32),
+                 o_tab = o_st + al(ns * sizeof(pf_climb_set)), total = o_tab + al(3 * ns * 4);
+    if (!B->c_mem) {
+        B->c_mem = pool_acquire(D, total, &B->c_cap);
+        if (!B->c_mem) return fail("pf_climb_batch: hipMalloc(%zu) failed", total);
+    }
+    uint8_t* cb = static_cast<uint8_t*>(B->c_mem);
+    pf_set_desc* d_wdescs = reinterpret_cast<pf_set_desc*>(cb + o_wd);
+    uint4* d_wschema = reinterpret_cast<uint4*>(cb + o_ws);
+    uint32_t* d_par[2] = {reinterpret_cast<uint32_t*>(cb + o_p0), reinterpret_cast<uint32_t*>(cb + o_p1)};
+    pf_climb_set* d_state = reinterpret_cast<pf_climb_set*>(cb + o_st);
+    uint32_t* d_wvoff = reinterpret_cast<uint32_t*>(cb + o_tab);
+    uint32_t *d_target = d_wvoff + ns, *d_req = d_target + ns;
+
+    // this call's sets in launch order: the 8-register ones, then the 16-register ones
+    std::vector<uint32_t> req;
+    req.reserve(n);
+    for (int part = 0; part < 2; ++part)
+        for (size_t i = 0; i < n; i++)
+            if ((int)B->h_wide[set_ids[i]] == part) req.push_back(set_ids[i]);
+    const size_t n_narrow = (size_t)std::count_if(req.begin(), req.end(), [&](uint32_t s) { return !B->h_wide[s]; });
+    std::vector<uint32_t> target(ns);
+    for (size_t s = 0; s < ns; s++) target[s] = PF_CLIMB_HOLDS * B->h_sites[s];
+
+    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
+    const size_t in_bytes = 3 * ns * 4, out_bytes = cbytes + ns * sizeof(pf_climb_set) + n_wvars * 32;
+    uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
+    if (!pin) return fail("pf_climb_batch: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
+    memcpy(pin, wvoff.data(), ns * 4);
+    memcpy(pin + ns * 4, target.data(), ns * 4);
+    memset(pin + 2 * ns * 4, 0, ns * 4);
+    memcpy(pin + 2 * ns * 4, req.data(), n * 4);
+    HIPCHK(hipMemcpyAsync(d_wvoff, pin, in_bytes, hipMemcpyHostToDevice, st));
+
+    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
+    uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
+    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
+    constexpr uint32_t n_queue = 2 * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;  // the heads of both parts
+    hipLaunchKernelGGL(pf_reset_kernel, dim3((PF_SCRATCH_BYTES / 4 + 255u) / 256u), dim3(256), 0, st, B->d_scratch,
+                       (uint32_t)(PF_SCRATCH_BYTES / 4), B->d_found, 0u);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B->ev0, st));
+    hipLaunchKernelGGL(pf_climb_init_kernel, dim3((uint32_t)n), dim3(64), 0, st, B->d_descs, B->d_schema, d_req,
+                       d_wvoff, d_target, d_wdescs, d_wschema, d_state);
+    HIPCHK(hipGetLastError());
+    const uint64_t deadline = timeout_ms ? (uint64_t)timeout_ms * 100000ull : 0ull;  // 100 MHz
+    // the rounds, back to back on the stream: nothing here waits for the device
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint64_t gs = global_seed + (uint64_t)(r + 1u) * PF_CLIMB_SEED_MUL;
+        const pf_set_desc* descs_r = r ? d_wdescs : B->d_descs;
+        const uint4* schema_r = r ? d_wschema : B->d_schema;
+        const uint32_t* parents_r = r ? d_par[r & 1u] : B->d_parents;
+        for (int part = 0; part < 2; ++part) {
+            const size_t first = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
+            if (np == 0) continue;
+            const uint64_t items = (uint64_t)np * groups;
+            const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early);
+            const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
+            hipLaunchKernelGGL(part == 0 ? pf_climb_kernel : pf_climb_r16_kernel, dim3(blocks),
+                               dim3(64 * PF_SEARCH_WG_WAVES), 0, st, descs_r, d_req + first, (uint32_t)np, B->d_code,
+                               B->d_consts, schema_r, parents_r, gs, per_round, groups, r ? 1u : 0u, deadline, d_t0,
+                               d_state, d_counters, d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(pf_climb_adopt_kernel, dim3((uint32_t)n), dim3(64), 0, st, descs_r, d_wdescs, d_req,
+                           B->d_code, B->d_consts, schema_r, parents_r, gs, r, d_par[r & 1u], d_par[(r + 1u) & 1u],
+                           d_state, d_queue, n_queue);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(B->ev1, st));
+    // counters, states and the final assignments (A_R, in buffer R & 1) in the staging buffer;
+    // the stream orders these copies after the upload above has been consumed
+    HIPCHK(hipMemcpyAsync(pin, B->d_scratch + PF_COUNTER_OFF / 4, cbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin + cbytes, d_state, ns * sizeof(pf_climb_set), hipMemcpyDeviceToHost, st));
+    if (n_wvars)
+        HIPCHK(hipMemcpyAsync(pin + cbytes + ns * sizeof(pf_climb_set), d_par[rounds & 1u], n_wvars * 32,
+                              hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long* hs = reinterpret_cast<const unsigned long long*>(pin);
+    const pf_climb_set* hst = reinterpret_cast<const pf_climb_set*>(pin + cbytes);
+    const uint32_t* hv = reinterpret_cast<const uint32_t*>(pin + cbytes + ns * sizeof(pf_climb_set));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
+        for (int k = 0; k < 4; k++) h[k] += hs[i * 16 + k];
+    uint64_t n_sat = 0;
+    size_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t s = set_ids[i];
+        if (status_out) status_out[i] = hst[s].status;
+        if (score_out) score_out[i] = hst[s].score;
+        if (round_out) round_out[i] = hst[s].round;
+        n_sat += hst[s].status == PF_CLIMB_WITNESS;
+        const size_t nv = B->h_descs[s].n_vars;
+        if (values_out && nv) memcpy(values_out + off * 8, hv + (size_t)wvoff[s] * 8, nv * 32);
+        off += nv;
+    }
+    if (stats) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+        stats->evals_full = h[0];
+        stats->cands_decided = h[1];
+        stats->n_sat = n_sat;
+        stats->kernel_ms = ms;
+        stats->timed_out = h[3] ? 1u : 0u;
+    }
     return 0;
 }
 

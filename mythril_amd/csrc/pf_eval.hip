@@ -429,8 +429,26 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
     return out;
 }
 
-enum Mode { MODE_GEN = 0, MODE_SOA = 1 };
+// MODE_CLIMB: MODE_GEN's candidates, no short-circuit, and the lane's score accumulated at the
+// assert sites (include/pf_bytecode.h, climb contract)
+enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2 };
 
+// Score of one fused compare-and-assert site (climb contract): PF_CLIMB_HOLDS where it holds,
+// else how near it is — EQ: PF_CLIMB_NEAR - popcount(a ^ b); ULT / ULE / SLT / SLE:
+// PF_CLIMB_NEAR - bitlen(|a - b|) = clz256(|a - b|) on the raw (zero-extended) operands;
+// any other compare: 0.  op is wave-uniform.
+PF_INL uint32_t climb_term(uint32_t op, const u256& x, const u256& y, uint32_t holds) {
+    uint32_t near = 0u;
+    if (op == PF_B_EQ) {
+        uint32_t pc = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) pc += (uint32_t)__builtin_popcount(x.l[i] ^ y.l[i]);
+        near = PF_CLIMB_NEAR - pc;
+    } else if (op >= PF_B_ULT && op <= PF_B_SLE) {
+        near = pf::clz256(pf::sel256(pf::ult256(x, y), pf::sub256(y, x), pf::sub256(x, y)));
+    }
+    return holds ? PF_CLIMB_HOLDS : near;
+}
 
 
 // Per-unit cycle accounting (profiling builds only, tools/unitprof.py): s_memtime deltas of
@@ -471,7 +489,8 @@ PF_INL uint2* exp_tbl_of(uint2* lds) {
 template <int MODE, int NREG>
 PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_t flags,
                             const uint32_t* __restrict__ soa, uint32_t soa_n,
-                            uint2* exp_tbl, uint32_t* complete, uint64_t* ops, UnitProf* prof) {
+                            uint2* exp_tbl, uint32_t* complete, uint64_t* ops, UnitProf* prof,
+                            uint32_t* score_out = nullptr) {
     // No initialisation: pf_batch_create rejects programs that read a register before
     // writing it, so the banks never leak values between candidates.
     constexpr int LPB = 16 / NREG;  // limbs per vector
@@ -503,7 +522,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #define PF_DO_ASSERT(v)                                                                       \
     do {                                                                                      \
         root &= (v);                                                                          \
-        if ((flags & PF_FLAG_SHORTCIRCUIT) &&                                                 \
+        if (MODE != MODE_CLIMB && (flags & PF_FLAG_SHORTCIRCUIT) &&                           \
             pf::wave_none(pf::wave_mask(root != 0u) & pf::wave_mask(active))) {               \
             In = make_uint4(PF_U_END << 21, 0u, 0u, 0u);                                      \
             sc = 1u;                                                                          \
@@ -519,6 +538,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #define PF_NEXT() continue
 #endif
     uint32_t root = 1u, sc = 0u;
+    uint32_t score = 0u;  // MODE_CLIMB only
     uint64_t cost = 0;
     // Software-pipelined fetch: the scalar load of instruction i+1 is issued while
     // instruction i executes.  The loop ends at PF_END (pf_batch_create checks that every
@@ -689,7 +709,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
             }
             case PF_U_GEN:
                 // ---- candidate generator (one site for W and B variables)
-                if (MODE == MODE_GEN) {
+                if (MODE != MODE_SOA) {
                     z = gen_var(S, aux, cand);
                 } else {
 #pragma unroll
@@ -726,6 +746,9 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                     }
                 }
                 BSET(d, bres);
+                if constexpr (MODE == MODE_CLIMB) {
+                    if (I.x & PF_I_ASSERT) score += climb_term(op, x, y, bres);
+                }
                 if (I.x & PF_I_ASSERT) PF_DO_ASSERT(bres);
                 PF_NEXT();
             }
@@ -752,8 +775,12 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                             spill[PF_SLOT(aux) * 8u] = BGET(a);
                         break;
                     default:  // PF_ASSERT
+                        if constexpr (MODE == MODE_CLIMB) score += BGET(a) * PF_CLIMB_HOLDS;
                         PF_DO_ASSERT(BGET(a));
                         PF_NEXT();
+                }
+                if constexpr (MODE == MODE_CLIMB) {
+                    if (I.x & PF_I_ASSERT) score += BGET(d) * PF_CLIMB_HOLDS;
                 }
                 if (I.x & PF_I_ASSERT) PF_DO_ASSERT(BGET(d));
                 PF_NEXT();
@@ -842,6 +869,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 program_end:
     *complete = sc ^ 1u;
     *ops += cost;
+    if constexpr (MODE == MODE_CLIMB) *score_out = score;
     return root;
 #undef BGET
 }
@@ -1060,6 +1088,225 @@ extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_
 }
 extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_check_early_r16_kernel(PF_CHECK_PARAMS) {
     check_body<true, 16>(PF_CHECK_ARGS);
+}
+
+// ---- climb: scored rounds over near misses (include/pf_bytecode.h, climb contract) ------
+// Per-set state of a climb, in the batch's climb block (pathfeas.hip).  `best` takes the waves'
+// 64-bit atomicMax of (score << 32) | ~candidate: the highest score, ties to the smallest
+// index; 0 = nothing posted this round (no candidate index is 0xFFFFFFFF).
+struct pf_climb_set {
+    unsigned long long best;
+    uint32_t status;  // PF_CLIMB_NONE while the set runs, else final
+    uint32_t cut;     // the deadline left a group of this round unevaluated
+    uint32_t score;   // of the current assignment
+    uint32_t round;   // the round that generated the current assignment ...
+    uint32_t index;   // ... and its candidate index there
+    uint32_t target;  // PF_CLIMB_HOLDS x assert sites: the score of a witness
+};
+static_assert(sizeof(pf_climb_set) == 32, "pathfeas.hip copies the states back as 8 u32 each");
+
+// One round of every climbed set: items (set, 64-candidate group) from the search's work queue
+// (the heads of one launch, zeroed before it).  A wave evaluates its group in scored mode,
+// reduces (score << 32) | ~cand to the wave's maximum and posts it with one atomicMax.  A set
+// that is finished costs its items one load each.  Once the deadline has passed, a wave
+// evaluates nothing more but still takes items, marking their sets cut: every group of a
+// running set is then either evaluated or accounted for, so the adopt kernel never takes
+// the best of part of a round for the round's best.
+template <int NREG>
+PF_INL void climb_body(const pf_set_desc* __restrict__ descs, const uint32_t* __restrict__ order, uint32_t n_sets,
+                       const uint4* __restrict__ code, const uint32_t* __restrict__ consts,
+                       const uint4* __restrict__ schema, const uint32_t* __restrict__ parents, uint64_t gseed,
+                       uint32_t per_round, uint32_t groups, uint32_t exclude0, uint64_t deadline_ticks,
+                       uint64_t* __restrict__ t0_slot, pf_climb_set* __restrict__ state,
+                       unsigned long long* __restrict__ counters, uint32_t* __restrict__ queue) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const uint32_t n_items = n_sets * groups;
+    __shared__ uint2 pf_exp_lds[PF_SEARCH_LDS_U2];
+    uint2* exp_tbl = exp_tbl_of(pf_exp_lds);
+
+    uint64_t t0 = 0;
+    if (deadline_ticks) {  // the first wave of the climb's first launch stamps the start (check_body)
+        uint64_t now = __builtin_amdgcn_s_memrealtime();
+        uint64_t prev = __hip_atomic_load(t0_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prev == 0) prev = atomicCAS((unsigned long long*)t0_slot, 0ull, (unsigned long long)now);
+        const uint64_t t = prev ? prev : now;
+        t0 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t) |
+             ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32);
+    }
+    UnitProf prof;
+#pragma unroll
+    for (int i = 0; i < PF_PROF_BUCKETS; i++) prof.c[i] = 0;
+    uint64_t decided = 0;
+    uint32_t cut = 0u;
+    for (uint32_t qi = 0; qi < PF_EARLY_QUEUES; ++qi) {
+        const uint32_t q = (wave + qi) % PF_EARLY_QUEUES;
+        const uint32_t nq = n_items > q ? (n_items - q + PF_EARLY_QUEUES - 1u) / PF_EARLY_QUEUES : 0u;
+        if (qi > 0u) {
+            uint32_t h = 0u;
+            if (lane == 0u) h = __hip_atomic_load(queue + q * PF_EARLY_QUEUE_STRIDE, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(h) >= nq) continue;
+        }
+        for (;;) {
+            uint32_t v = 0u;
+            if (lane == 0u) v = atomicAdd(queue + q * PF_EARLY_QUEUE_STRIDE, 1u);
+            const uint32_t k = __builtin_amdgcn_readfirstlane(v);
+            if (k >= nq) break;
+            const uint32_t item = k * PF_EARLY_QUEUES + q;
+            const uint32_t set = __builtin_amdgcn_readfirstlane(order[item % n_sets]);
+            const uint32_t group = item / n_sets;
+            pf_climb_set* cs = state + set;
+            const uint32_t fin = __hip_atomic_load(&cs->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(fin) != PF_CLIMB_NONE) continue;
+            if (deadline_ticks && !cut && __builtin_amdgcn_s_memrealtime() - t0 > deadline_ticks) cut = 1u;
+            if (cut) {
+                if (lane == 0u) atomicOr(&cs->cut, 1u);
+                continue;
+            }
+            const uint32_t cand = group * 64u + lane;
+            const bool active = cand < per_round;
+            uint32_t complete = 0, score = 0;
+            uint64_t lane_ops = 0;
+            (void)run_program<MODE_CLIMB, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), cand,
+                                                active, 0u, nullptr, 0u, exp_tbl, &complete, &lane_ops, &prof,
+                                                &score);
+            // from round 1 on candidate 0 is the current assignment itself: not a move
+            const bool counts = active && !(exclude0 && cand == 0u);
+            uint64_t key = counts ? ((uint64_t)score << 32) | (uint64_t)(~cand) : 0ull;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), o) << 32) |
+                                       (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)key, o);
+                key = other > key ? other : key;
+            }
+            if (lane == 0u && key) atomicMax(&cs->best, (unsigned long long)key);
+            decided += __popcll(pf::wave_mask(active));
+        }
+    }
+    if (lane == 0) {
+        unsigned long long* cl = counters + PF_COUNTER_OFF / 8 + (wave % PF_COUNTER_STRIPES) * 16u;
+        if (decided) {  // no short-circuit in a scored run: every decided lane ran the whole program
+            atomicAdd(cl + 0, (unsigned long long)decided);
+            atomicAdd(cl + 1, (unsigned long long)decided);
+        }
+        if (cut) atomicAdd(cl + 3, 1ull);
+    }
+}
+
+#define PF_CLIMB_PARAMS                                                                       \
+    const pf_set_desc *__restrict__ descs, const uint32_t *__restrict__ order, uint32_t n_sets, \
+        const uint4 *__restrict__ code, const uint32_t *__restrict__ consts,                   \
+        const uint4 *__restrict__ schema, const uint32_t *__restrict__ parents, uint64_t gseed, \
+        uint32_t per_round, uint32_t groups, uint32_t exclude0, uint64_t deadline_ticks,       \
+        uint64_t *__restrict__ t0_slot, pf_climb_set *__restrict__ state,                      \
+        unsigned long long *__restrict__ counters, uint32_t *__restrict__ queue
+#define PF_CLIMB_ARGS                                                                         \
+    descs, order, n_sets, code, consts, schema, parents, gseed, per_round, groups, exclude0,  \
+        deadline_ticks, t0_slot, state, counters, queue
+
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_climb_kernel(PF_CLIMB_PARAMS) {
+    climb_body<PF_NW_NARROW + 1>(PF_CLIMB_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_climb_r16_kernel(PF_CLIMB_PARAMS) {
+    climb_body<16>(PF_CLIMB_ARGS);
+}
+
+// Before a climb's first round, one block per climbed set: the set's working descriptor and
+// schema — its own, with rows wvoff[set].. of the parent buffers as every variable's parent
+// slot — and its state reset (target[set] = the score of a witness).
+extern "C" __global__ void __launch_bounds__(64)
+pf_climb_init_kernel(const pf_set_desc* __restrict__ descs, const uint4* __restrict__ schema,
+                     const uint32_t* __restrict__ req_sets, const uint32_t* __restrict__ wvoff,
+                     const uint32_t* __restrict__ target, pf_set_desc* __restrict__ wdescs,
+                     uint4* __restrict__ wschema, pf_climb_set* __restrict__ state) {
+    const uint32_t set = req_sets[blockIdx.x];
+    pf_set_desc D = descs[set];
+    const uint32_t voff = wvoff[set];
+    for (uint32_t v = threadIdx.x; v < D.n_vars; v += blockDim.x) {
+        uint4 sc = schema[D.var_off + v];
+        sc.w = voff + v;
+        wschema[voff + v] = sc;
+    }
+    if (threadIdx.x == 0u) {
+        D.var_off = voff;
+        D.parent_off = voff;
+        wdescs[set] = D;
+        pf_climb_set z;
+        z.best = 0ull;
+        z.status = PF_CLIMB_NONE;
+        z.cut = 0u;
+        z.score = 0u;
+        z.round = 0u;
+        z.index = 0u;
+        z.target = target[set];
+        state[set] = z;
+    }
+}
+
+// After a round's climb launches, one block per climbed set: the round's best against the
+// current score, A_{r+1} into par_next (one thread per variable; the best candidate's values
+// are regenerated with gen_var under the round's inputs, which read A_r — hence the other
+// buffer), the state's record of it, and the slot cleared for the next round.  Block 0 also
+// zeroes the work-queue heads the next round's launches start from.
+// descs / schema / parents: what the round generated from (round 0: the batch's own; later: the
+// working copies over par_cur); wdescs[set].var_off: the set's rows in par_cur / par_next.
+extern "C" __global__ void __launch_bounds__(64)
+pf_climb_adopt_kernel(const pf_set_desc* __restrict__ descs, const pf_set_desc* __restrict__ wdescs,
+                      const uint32_t* __restrict__ req_sets, const uint4* __restrict__ code,
+                      const uint32_t* __restrict__ consts, const uint4* __restrict__ schema,
+                      const uint32_t* __restrict__ parents, uint64_t gseed, uint32_t round,
+                      const uint32_t* __restrict__ par_cur, uint32_t* __restrict__ par_next,
+                      pf_climb_set* __restrict__ state, uint32_t* __restrict__ queue, uint32_t n_queue) {
+    const uint32_t set = req_sets[blockIdx.x];
+    pf_climb_set* cs = state + set;
+    const unsigned long long key = cs->best;
+    const uint32_t status = cs->status, cutf = cs->cut, cur = cs->score;
+    __syncthreads();  // every thread holds the state that thread 0 rewrites below
+    const bool live = status == PF_CLIMB_NONE, is_cut = live && cutf != 0u;
+    const uint32_t sc = (uint32_t)(key >> 32), cand = ~(uint32_t)key;
+    // sideways moves are taken (>=); round 0 starts from score 0, so its best is always adopted
+    const bool adopt = live && !is_cut && key != 0ull && sc >= cur;
+    const pf_set_desc D = descs[set];
+    const uint32_t voff = wdescs[set].var_off;
+    SetCtx S;
+    S.code = code + D.code_off;
+    S.consts = consts + (size_t)D.const_off * 8u;
+    S.schema = schema + D.var_off;
+    S.parents = parents;
+    S.n_ins = D.n_ins;
+    S.n_const = D.n_const;
+    S.n_vars = D.n_vars;
+    S.seed = D.seed;
+    S.k0 = (uint32_t)gseed ^ D.seed;
+    S.k1 = (uint32_t)(gseed >> 32);
+    S.nc_rcp = D.n_const ? urcp32(D.n_const) : 0u;
+    for (uint32_t v = threadIdx.x; v < D.n_vars; v += blockDim.x) {
+        u256 x;
+        if (adopt || round == 0u) {  // round 0 has no A_0 to keep: candidate 0 stands in (a cut set)
+            x = gen_var(S, v, adopt ? cand : 0u);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) x.l[i] = par_cur[((size_t)voff + v) * 8u + i];
+        }
+        uint32_t* o = par_next + ((size_t)voff + v) * 8u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) o[i] = x.l[i];
+    }
+    if (threadIdx.x == 0u) {
+        if (adopt) {
+            cs->score = sc;
+            cs->round = round;
+            cs->index = cand;
+            if (sc == cs->target) cs->status = PF_CLIMB_WITNESS;
+        } else if (is_cut) {
+            cs->status = PF_CLIMB_CUT;
+        }
+        cs->best = 0ull;
+        cs->cut = 0u;
+    }
+    if (blockIdx.x == 0u)
+        for (uint32_t i = threadIdx.x; i < n_queue; i += blockDim.x) queue[i] = 0u;
 }
 
 // ---- explicit-assignment evaluation (SoA [var][limb][cand]) --------------------------

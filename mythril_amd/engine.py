@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .ir import LIMBS, Batch, Program, from_limbs
+from .ir import CLIMB_WITNESS, LIMBS, Batch, Program, from_limbs
 
 NOT_FOUND = 0xFFFFFFFF
 
@@ -36,6 +36,22 @@ class CheckResult:
     @property
     def sat(self) -> np.ndarray:
         return self.found != NOT_FOUND
+
+
+@dataclass
+class ClimbResult:
+    """Engine.climb: one entry per requested set, in request order."""
+    status: np.ndarray       # uint32 ir.CLIMB_NONE / CLIMB_WITNESS / CLIMB_CUT
+    score: np.ndarray        # uint32 score of the final assignment
+    round: np.ndarray        # uint32 the round that generated it
+    values: list             # per set: its final assignment as limb rows [n_vars, 8] uint32
+    evals: int = 0           # candidate evaluations over all rounds
+    kernel_ms: float = 0.0
+    timed_out: bool = False
+
+    @property
+    def sat(self) -> np.ndarray:
+        return self.status == CLIMB_WITNESS
 
 
 class DeviceBatch:
@@ -178,6 +194,53 @@ class Engine:
             res.append([from_limbs(rows[off + i]) for i in range(k)])
             off += k
         return res
+
+    def climb(self, db, set_ids: Sequence[int], rounds: int, per_round: int, seed: int = 0,
+              timeout_ms: int = 0) -> ClimbResult:
+        """Climb the given sets (pf_climb_batch; include/pf_bytecode.h, climb contract):
+        ``rounds`` scored searches of ``per_round`` candidates, each round's best near miss
+        the parent model of the next.  ``db`` is one DeviceBatch, or the list upload_sharded
+        returned — ``set_ids`` then index the concatenation of its batches, as check_many's
+        verdicts do, and every set is climbed on the batch that holds it."""
+        dbs = list(db) if isinstance(db, (list, tuple)) else [db]
+        ids = [int(s) for s in set_ids]
+        n = len(ids)
+        status = np.zeros(n, dtype=np.uint32)
+        score = np.zeros(n, dtype=np.uint32)
+        rnd = np.zeros(n, dtype=np.uint32)
+        values: List[Optional[np.ndarray]] = [None] * n
+        total = sum(len(d) for d in dbs)
+        if len(dbs) > 1:   # one batch: pf_climb_batch checks its own ids; several: none may fall through
+            for s in ids:
+                if not 0 <= s < total:
+                    raise _lib.PathFeasError(f"climb: set {s} out of range ({total} sets)")
+        evals = 0
+        ms = 0.0
+        cut = False
+        base = 0
+        for d in dbs:
+            mine = list(range(n)) if len(dbs) == 1 else [i for i, s in enumerate(ids) if base <= s < base + len(d)]
+            if mine or len(dbs) == 1:
+                local = np.array([(ids[i] - base) & 0xFFFFFFFF for i in mine], dtype=np.uint32)
+                nv = [int(d.batch.descs[s][5]) if s < len(d) else 0 for s in local]
+                st_, sc_, rd_ = (np.zeros(max(len(mine), 1), dtype=np.uint32) for _ in range(3))
+                vals = np.zeros(max(sum(nv), 1) * LIMBS, dtype=np.uint32)
+                st = _lib.pf_stats()
+                _lib.check(_lib.lib().pf_climb_batch(
+                    d.handle, seed, rounds, per_round, timeout_ms,
+                    _lib.ptr_u32(local) if len(mine) else None, len(mine), _lib.ptr_u32(st_),
+                    _lib.ptr_u32(sc_), _lib.ptr_u32(rd_), _lib.ptr_u32(vals), ctypes.byref(st)),
+                    "pf_climb_batch")
+                rows, off = vals.reshape(-1, LIMBS), 0
+                for j, i in enumerate(mine):
+                    status[i], score[i], rnd[i] = st_[j], sc_[j], rd_[j]
+                    values[i] = rows[off:off + nv[j]].copy()
+                    off += nv[j]
+                evals += st.cands_decided
+                ms += st.kernel_ms
+                cut = cut or bool(st.timed_out)
+            base += len(d)
+        return ClimbResult(status, score, rnd, values, evals, ms, cut)
 
     def materialize_limbs(self, db: DeviceBatch, set_ids: Sequence[int], cand_ids: Sequence[int],
                           seed: int = 0) -> np.ndarray:

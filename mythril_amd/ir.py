@@ -120,6 +120,26 @@ FLAG_EARLY_EXIT = 2
 FLAG_COUNT_OPS = 4
 FLAG_NO_PROBE = 8     # include/pf_bytecode.h: skip the candidate-0 probe launch
 
+# ---- climb contract (include/pf_bytecode.h) -----------------------------------------
+# A climb is `rounds` scored searches of `per_round` candidates under the unchanged generator
+# contract; each round's best near miss is every variable's parent in the next.  Score of a
+# candidate on the device program: per assert site CLIMB_HOLDS if it holds, else for a fused
+# EQ CLIMB_NEAR - popcount(a ^ b), for a fused ULT / ULE / SLT / SLE CLIMB_NEAR -
+# bitlen(|a - b|) on the zero-extended register values, else 0; CLIMB_HOLDS x sites is a
+# witness.  Best = highest score, ties to the smallest index, candidate 0 left out from round 1
+# on; adopted when its score >= the current one (0 before round 0).
+CLIMB_NONE = 0        # pf_climb_status: all rounds run, no witness
+CLIMB_WITNESS = 1
+CLIMB_CUT = 2         # the device deadline cut a round of the set
+CLIMB_HOLDS = 512
+CLIMB_NEAR = 256
+CLIMB_SEED_MUL = 0x9E3779B97F4A7C15
+
+
+def climb_round_seed(seed: int, r: int) -> int:
+    """Global seed of round ``r`` of a climb with global seed ``seed``."""
+    return (seed + (r + 1) * CLIMB_SEED_MUL) & 0xFFFFFFFFFFFFFFFF
+
 # ---- algorithmic int32-op cost table (SURVEY.md §8(d)) -----------------------------
 # Ops not in the table (moves, constant loads, candidate generation) cost 0: they are
 # bookkeeping, not constraint arithmetic.  Width-generic ops scale by ceil(w/32)/8.

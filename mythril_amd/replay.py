@@ -32,14 +32,16 @@ from .smt import terms as T
 PHASES = ("read", "recover", "lower", "search", "recheck")
 # check_sets' own phases (gpu_check.STATS.phase_s) under the report's names
 _CHECK_PHASE = {"bucket": "lower", "lower": "lower", "probe": "search", "upload": "search",
-                "search": "search", "materialize": "search", "recheck": "recheck", "models": "recheck"}
+                "search": "search", "climb": "search", "materialize": "search", "recheck": "recheck",
+                "models": "recheck"}
 
 
 @dataclass
 class FileResult:
     name: str
     cls: str = "unknown"                 # "sat" | "unknown" | "objective" | "error: <text>"
-    origin: Optional[str] = None         # witness provenance (gpu_check._origin) of a sat file
+    origin: Optional[str] = None         # witness provenance (gpu_check._origin) of a sat file:
+                                         # "climb" / "search" / "hint" / "parent" / "first" / "cache"
     ms: float = 0.0                      # read + recover + re-check, plus the file's share of its group's check_sets
     model: Optional[object] = None       # the WitnessModel of a sat file
     query: Optional[smtlib.Query] = None
@@ -315,6 +317,20 @@ def replay_dir(path: str, config=None, models_dir: Optional[str] = None,
     return rep
 
 
+def _climb_arg(text: str) -> Tuple[int, Optional[int]]:
+    """``ROUNDS`` or ``ROUNDS:CANDIDATES`` of ``--climb``."""
+    import argparse
+
+    head, _, tail = text.partition(":")
+    try:
+        rounds, cands = int(head), (int(tail) if tail else None)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected ROUNDS[:CANDIDATES], got {text!r}")
+    if rounds < 0 or (cands is not None and cands < 1):
+        raise argparse.ArgumentTypeError(f"expected ROUNDS >= 0 and CANDIDATES >= 1, got {text!r}")
+    return rounds, cands
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     import argparse
 
@@ -328,8 +344,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--timeout-ms", type=int, default=gpu_check.CONFIG.timeout_ms)
     ap.add_argument("--models", metavar="DIR", help="write <name>.model.smt2 witness certificates here")
     ap.add_argument("--workers", type=int, default=None, help="reader processes (at most min(16, CPUs allowed))")
+    ap.add_argument("--climb", metavar="ROUNDS[:CANDIDATES]", type=_climb_arg, default=None,
+                    help="climb the buckets the search finds nothing for: ROUNDS scored rounds of CANDIDATES "
+                         f"candidates (default {gpu_check.CONFIG.climb_candidates}); files answered that way "
+                         "report the origin \"climb\"")
     args = ap.parse_args(argv)
     cfg = replace(gpu_check.CONFIG, budget=args.budget, timeout_ms=args.timeout_ms)
+    if args.climb is not None:
+        cfg = replace(cfg, climb_rounds=args.climb[0],
+                      climb_candidates=args.climb[1] if args.climb[1] is not None else cfg.climb_candidates)
     rep = replay_dir(args.dir, config=cfg, models_dir=args.models, workers=args.workers)
     lines = rep.json_lines()
     if args.out:

@@ -78,6 +78,13 @@ class GpuConfig:
     # ... for calls of at most this many programs (a single query's buckets: latency); a
     # batch's search runs its long programs side by side anyway
     probe_max_progs: int = 4
+    # climb (include/pf_bytecode.h, climb contract): buckets the search found nothing for go
+    # through `climb_rounds` scored rounds of `climb_candidates` candidates, each round's best
+    # near miss the next round's parent model — in the same call, on the batch still
+    # resident.  0 rounds = off, the default: answers then are the plain search's.  Recommended
+    # where it is on: 16 rounds x 2,048 candidates (profiles/r11_climb.md).
+    climb_rounds: int = int(os.environ.get("PF_CLIMB_ROUNDS", "0"))
+    climb_candidates: int = int(os.environ.get("PF_CLIMB_CANDIDATES", "2048"))
 
 
 CONFIG = GpuConfig()
@@ -95,6 +102,8 @@ class GpuStats:
     recheck_failures: int = 0  # GPU witnesses the host re-check rejected (must stay 0)
     probe_split: int = 0       # long buckets whose candidate 0 went through the conjunct probe
     probe_split_sat: int = 0   # ... and held there (no search launch for them)
+    climbed: int = 0           # buckets without a search witness that went through the climb
+    climb_sat: int = 0         # ... and got a witness there
     kernel_ms: float = 0.0
     evals: int = 0
     host_s: float = 0.0      # lowering + hints + witness re-checks
@@ -140,7 +149,10 @@ def _neg_key(key: tuple, cfg: GpuConfig) -> tuple:
     # parents only seed candidate 0 of a bucket's first search; a bucket whose complete
     # search found nothing stays negative (as the reference's lru_cache'd check_quick_sat
     # keeps its negative answers, support_utils.py:59)
-    return (key, cfg.budget, cfg.seed, cfg.flags, cfg.hints)
+    # ... under this configuration: a bucket the climb also left unanswered is negative only
+    # for searches that climb the same way
+    climb = (cfg.climb_rounds, cfg.climb_candidates) if cfg.climb_rounds > 0 else (0, 0)
+    return (key, cfg.budget, cfg.seed, cfg.flags, cfg.hints) + climb
 
 
 def note_values(vals: Dict[str, int], cfg: Optional[GpuConfig] = None) -> None:
@@ -359,10 +371,15 @@ def _lower_bucket(bucket: List[T.Term], reg: UFRegistry, parent: Optional[dict],
     return lo, lower(lo.dag, seed=_set_seed(bucket))
 
 
+_CLIMB_IDX = 0xFFFFFFFE   # found_all[] of a bucket whose witness is a climb's assignment
+
+
 def _origin(idx: int, prog, hinted: bool, parented: bool) -> str:
-    """Provenance of a bucket witness: "search" = a later GPU candidate; candidate 0 is the
-    host hint model ("hint"), the parent model ("parent") or the generator's first
-    candidate ("first")."""
+    """Provenance of a bucket witness: "climb" = the assignment a climb ended on; "search" = a
+    later GPU candidate; candidate 0 is the host hint model ("hint"), the parent model
+    ("parent") or the generator's first candidate ("first")."""
+    if idx == _CLIMB_IDX:
+        return "climb"
     if idx > 0:
         return "search"
     if prog.has_parent:
@@ -591,6 +608,7 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
         for k in pre:
             found_all[k] = 0
         timed_out = False
+        climb_ms, climb_evals = 0.0, 0
         vals_of = {}
         limb_rows = []   # native: the witnesses' variables as limbs, in `sat` order
         if search:
@@ -603,6 +621,7 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                 # the device's candidate-0 probe launch would walk that long program once in
                 # vain before the search walks it again
                 flags |= ir.FLAG_NO_PROBE
+            t_dev = time.perf_counter()
             if len(dbs) == 1:
                 res = eng.check(dbs[0], budget=cfg.budget, seed=cfg.seed, flags=flags,
                                 timeout_ms=cfg.timeout_ms)
@@ -614,6 +633,37 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
             for i, k in enumerate(search):
                 found_all[k] = res.found[i]
             ssat = [i for i in range(len(search)) if res.found[i] != 0xFFFFFFFF]
+            missed = [i for i in range(len(search)) if res.found[i] == 0xFFFFFFFF]
+            climb_on = cfg.climb_rounds > 0 and cfg.climb_candidates > 0 and missed and not timed_out \
+                and hasattr(eng, "climb")
+            # one deadline for the call's device work: the climb gets what the search left of
+            # timeout_ms (its launches stamp a start of their own), and none of it left means
+            # no climb — the buckets are then not complete answers of this configuration
+            climb_ms_left = 0
+            if climb_on and cfg.timeout_ms:
+                climb_ms_left = cfg.timeout_ms - int(1e3 * (time.perf_counter() - t_dev)) - 1
+                if climb_ms_left < 1:
+                    climb_on, timed_out = False, True
+            if climb_on:
+                # the near misses of the buckets the search left: a climb's witness is an
+                # assignment (no candidate index of the search), taken from here on like any
+                # other witness — re-checked on the host, cached, noted
+                cl = eng.climb(dbs if len(dbs) > 1 else dbs[0], missed, cfg.climb_rounds,
+                               cfg.climb_candidates, seed=cfg.seed, timeout_ms=climb_ms_left)
+                timed_out = timed_out or bool(cl.timed_out)
+                n_climb_sat = 0
+                for j, i in enumerate(missed):
+                    if int(cl.status[j]) == ir.CLIMB_WITNESS:
+                        rows = np.asarray(cl.values[j], dtype=np.uint32).reshape(-1, 8)
+                        vals_of[search[i]] = rows if nat else [ir.from_limbs(r) for r in rows]
+                        found_all[search[i]] = _CLIMB_IDX
+                        n_climb_sat += 1
+                climb_ms += cl.kernel_ms
+                climb_evals += cl.evals
+                with _lock:
+                    STATS.climbed += len(missed)
+                    STATS.climb_sat += n_climb_sat
+                lap("climb")
             base = 0
             for db in dbs:
                 mine = [i for i in ssat if base <= i < base + len(db)]
@@ -715,11 +765,13 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
         if ok:
             out[i] = WitnessModel(w, list(sets[i]))
             out[i].parts, out[i].reg = parts, reg    # the native witness's ingredients (model_cache)
-            # per bucket: _origin(); the set takes the strongest of its buckets: "search" if
+            # per bucket: _origin(); the set takes the strongest of its buckets: "climb" if some
+            # bucket needed one, else "search" if
             # some bucket needed a later candidate, else "hint" / "parent" / "first" if such a
             # candidate 0 answered some bucket, else "cache"
             kinds = {origin.get(k, "cache") for k in ks}
-            out[i].origin = next((c for c in ("search", "hint", "parent", "first") if c in kinds), "cache")
+            out[i].origin = next((c for c in ("climb", "search", "hint", "parent", "first") if c in kinds),
+                                 "cache")
             n_sat += 1
     lap("models")
     with _lock:
@@ -733,7 +785,7 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
         STATS.buckets += len(progs)
         STATS.bucket_hits += hits
         if res is not None:
-            STATS.kernel_ms += res.kernel_ms
-            STATS.evals += res.cands_decided
-        STATS.host_s += time.perf_counter() - t0 - (res.kernel_ms / 1e3 if res is not None else 0.0)
+            STATS.kernel_ms += res.kernel_ms + climb_ms
+            STATS.evals += res.cands_decided + climb_evals
+        STATS.host_s += time.perf_counter() - t0 - ((res.kernel_ms + climb_ms) / 1e3 if res is not None else 0.0)
     return out

@@ -224,15 +224,16 @@ PF_INL uint32_t sat_u32(double x) {
 // ---- products ---------------------------------------------------------------------
 // Product scanning (column by column) with a 96-bit column accumulator (acc, hi): every
 // partial product is one v_mad_u64_u32 into acc, and while a column's carry can still
-// reach limb 7 its carry out of bit 63 is added into hi.  The columns are inline-asm
+// reach limb 7 its carry out of bit 63 is added into hi, which each carrying column creates
+// (its first carry add is 0 + 0 + carry: nothing zeroes hi between columns; the one zero is
+// the first column's, which cannot carry).  The columns are inline-asm
 // blocks generated by tools/gen_u256_cols.py (u256_cols.h), which also places the gfx950
 // SGPR write->read wait states and, from the same columns, the truncated multiply-adds of
 // EXP's series (tmulk, below at tmul_add); under PF_HOST_MAC the columns are portable C, so
 // tools/u256_host_check.cpp and tools/exp_series_host.cpp run this header on the CPU.
 #define PF_COL_NEXT(k)                                   \
     r.l[k] = (uint32_t)acc;                              \
-    acc = (acc >> 32) | ((uint64_t)hi << 32);            \
-    hi = 0u;
+    acc = (acc >> 32) | ((uint64_t)hi << 32);
 
 // truncated 256 x 256 -> 256 product: 36 partial products
 PF_INL u256 mul256(const u256& a, const u256& b) {
@@ -645,20 +646,27 @@ PF_INL u256 exp256(const u256& base, const u256& e, uint32_t nbits, uint2* tbl, 
 // base^e for an exponent that fits one 32-bit word (the low part e0 of the 2-adic split):
 // the same windowed loop with the digits taken from that word — no 256-bit shifted exponent
 // live across the squarings (8 VGPRs fewer at the kernel's peak)
+// `want_b2` (wave-uniform): the caller reads base^2 back from entry 2 afterwards.
 template <int WB = 2>
-PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, uint2* tbl, uint32_t stride) {
+PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, bool want_b2, uint2* tbl, uint32_t stride) {
     static_assert(WB == 2, "window");
     // The table holds base^1..base^3 in entries 1..3 (entry 0 is not the table's: the
-    // narrow kernels keep a W register there, pf_eval.hip); digit 0 selects 1.  It is built
-    // even when every lane's e is 0: exp256_split reads base^2 back from entry 2 (base itself
-    // is then dead across the loop).
+    // narrow kernels keep a W register there, pf_eval.hip); digit 0 selects 1.  Only what is
+    // read is built: with nbits <= 1 every lane's e is 0 or 1 and the result comes straight
+    // from registers, and base^2 is then formed only for the caller (exp256_split's series
+    // reads it from entry 2; base itself is dead across the loop).
     u256 one = zero256();
     one.l[0] = 1u;
-    tbl_put(tbl, stride, 1u, base);
-    const u256 b2 = sqr256(base);
-    tbl_put(tbl, stride, 2u, b2);
-    tbl_put(tbl, stride, 3u, mul256(b2, base));
-    if (nbits == 0u) return one;
+    const bool loop = nbits > 1u;
+    if (loop || want_b2) {
+        const u256 b2 = sqr256(base);
+        tbl_put(tbl, stride, 2u, b2);
+        if (loop) {
+            tbl_put(tbl, stride, 1u, base);
+            tbl_put(tbl, stride, 3u, mul256(b2, base));
+        }
+    }
+    if (!loop) return sel256((uint32_t)(e == 0u), one, base);
     const uint32_t nd = (nbits + WB - 1u) / WB;  // digits
     uint32_t d = (e >> (WB * (nd - 1u))) & 3u;
     u256 r = sel256((uint32_t)(d == 0u), one, tbl_get(tbl, stride, d));
@@ -836,10 +844,11 @@ constexpr k256 exp_addend(int i, int j, int limbs) {
 
 // a * b + k mod 2^(32 L) (limbs >= L of the result zero; limbs >= L of a and k ignored), b of
 // LY = L or L - 1 limbs (its limbs >= LY ignored: zero): product scanning with k as the column
-// accumulator's starting value (u256_cols.h, tmulk; K0, K1 repeat k's two low limbs).  The
+// accumulator's starting value and its further limbs literals of the columns' adds
+// (u256_cols.h, tmulk; K0 .. K6 repeat k's limbs as constants).  The
 // full-width levels keep mul256 and one add256: the same products with the addend inside cost
 // 8 VALU less per EXP and a spilled register in the interpreter loop.
-template <int L, int LY, uint32_t K0, uint32_t K1>
+template <int L, int LY, uint32_t K0, uint32_t K1, uint32_t K2, uint32_t K3, uint32_t K4, uint32_t K5, uint32_t K6>
 PF_INL u256 tmul_add(const u256& a, const u256& b, const k256& k) {
     if constexpr (L >= 8) {
         u256 kk;
@@ -848,7 +857,7 @@ PF_INL u256 tmul_add(const u256& a, const u256& b, const k256& k) {
         return add256(mul256(a, b), kk);
     } else {
         u256 r = zero256();
-        tmulk<L, LY, K0, K1>(a.l, b.l, k.l, r.l);
+        tmulk<L, LY, K0, K1, K2, K3, K4, K5, K6>(a.l, b.l, r.l);
         return r;
     }
 }
@@ -859,7 +868,7 @@ PF_INL u256 tmul(const u256& a, const u256& b) {
     if constexpr (L >= 8)
         return mul256(a, b);
     else
-        return tmul_add<L, L, 0u, 0u>(a, b, k256{});
+        return tmul_add<L, L, 0u, 0u, 0u, 0u, 0u, 0u, 0u>(a, b, k256{});
 }
 
 // a - b * c mod 2^(32 L), c a small constant
@@ -919,7 +928,7 @@ PF_INL u256 horner(u256& g, const u256& tt) {
 #pragma unroll
         for (int i = 0; i < L; i++) inner.l[i] = C.l[i];
     }
-    return tmul_add<L, LY, K.l[0], K.l[1]>(shl_const<S, L>(g), inner, K);
+    return tmul_add<L, LY, K.l[0], K.l[1], K.l[2], K.l[3], K.l[4], K.l[5], K.l[6]>(shl_const<S, L>(g), inner, K);
 }
 
 // pt (profiling builds, tools/unitprof.py): s_memtime cycles of the three parts —
@@ -954,16 +963,19 @@ PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t s
     for (int i = 0; i < 8; i++)
         e0.l[i] = 32 * i + 32 <= M ? e.l[i] : (32 * i < M ? e.l[i] & ((1u << (M % 32)) - 1u) : 0u);
     const uint32_t nb0 = wave_max_u32(256u - clz256(e0));
-    u256 r;
-    if constexpr (M <= 32 && WB == 2)
-        r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
-    else
-        r = exp256<WB>(base, e0, nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
-    PF_EXP_STAMP(0)
     u256 n = shr256(e, (uint32_t)M, 0u);
 #pragma unroll
     for (int i = 0; i < 8; i++) n.l[i] = i < TL - 1 ? n.l[i] : (i == TL - 1 ? n.l[i] & TM : 0u);
-    if (wave_any(wave_mask(odd != 0u) & ~wave_mask(iszero256(n) != 0u))) {
+    // the series runs if some lane has an odd base and n != 0: known before the windowed part,
+    // which forms base^2 for it where its own table does not need one
+    const bool series = wave_any(wave_mask(odd != 0u) & ~wave_mask(iszero256(n) != 0u));
+    u256 r;
+    if constexpr (M <= 32 && WB == 2)
+        r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, series && TB == 8, tbl, stride);
+    else
+        r = exp256<WB>(base, e0, nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
+    PF_EXP_STAMP(0)
+    if (series) {
         // b^e0 waits in the LDS table's entry 1 (base^1, no longer needed) while the t
         // recurrence and the Horner chain run: 8 VGPRs fewer at their peak
         tbl_put(tbl, stride, 1u, r);

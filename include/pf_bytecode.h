@@ -192,6 +192,22 @@ static inline uint32_t pf_op_traffic(uint32_t op) {
         return PF_TR_RA | PF_TR_RB;
     return 0u;
 }
+
+/* fields of an instruction (host side; the kernel keeps its own decode): of w0 ... */
+static inline uint32_t pf_ins_op(uint32_t w0) { return w0 & 0xffu; }
+static inline uint32_t pf_ins_width(uint32_t w0) { return (w0 >> 8) & 0x3ffu; }
+static inline uint32_t pf_ins_traffic(uint32_t w0) { return (w0 >> 18) & 7u; }
+/* ... w0 with the traffic and unit bits recomputed from its opcode, every device flag cleared */
+static inline uint32_t pf_ins_stamp(uint32_t w0) {
+    return (w0 & 0x3ffffu) | (pf_op_traffic(w0 & 0xffu) << 18) | (pf_op_unit(w0 & 0xffu) << 21);
+}
+/* ... and of w1: the register fields, and w1 with operand a / b replaced */
+static inline uint32_t pf_ins_dst(uint32_t w1) { return w1 & 0xffu; }
+static inline uint32_t pf_ins_a(uint32_t w1) { return (w1 >> 8) & 0xffu; }
+static inline uint32_t pf_ins_b(uint32_t w1) { return (w1 >> 16) & 0xffu; }
+static inline uint32_t pf_ins_c(uint32_t w1) { return w1 >> 24; }
+static inline uint32_t pf_ins_with_a(uint32_t w1, uint32_t a) { return (w1 & ~0xff00u) | (a << 8); }
+static inline uint32_t pf_ins_with_b(uint32_t w1, uint32_t b) { return (w1 & ~0xff0000u) | (b << 16); }
 #endif
 
 /* B results are the opcodes PF_B_CONST..PF_B_FILL (a B destination register is written) */

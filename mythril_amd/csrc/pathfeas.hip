@@ -15,23 +15,29 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/pathfeas.h"
+#include "pf_devprog.h"
 #include "pf_eval.hip"
-#include "pf_fold.h"
 #include "pf_keccak.hip"
 
 namespace {
 
+// the host half — validator, device-program rewrites, threaded preparation, wave order
+using namespace pf_devprog;
+
 std::mutex g_mu;
 thread_local std::string g_err_tls;
 std::string g_err;
-// host work done outside g_mu (pf_batch_create's program checks) reports into t_err, moved
-// into g_err under the lock afterwards
-thread_local bool t_defer_err = false;
-thread_local std::string t_err;
+// g_err is written under g_mu only.  Work done without the lock (pf_devprog.h's preparation,
+// pf_batch_create's device lookup and upload) returns its error as a string, which its caller
+// moves into g_err under the lock (set_err).
+int set_err(const std::string& e) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_err = e;
+    return -1;
+}
 
 // One entry per initialised device (pf_init's mask): its library stream, timing events for
 // the Keccak launches and the launch geometry inputs.  Batches live on one device each and
@@ -86,24 +92,8 @@ uint32_t g_early_chunk_groups = 8;
 // a host hint model that leaves a root false — the probe of a long program then only delays
 // the search behind it; profiles/r06_probe_rule.md).
 uint32_t g_probe_max_sets = 64;
-// PF_DEVICE_FOLD: the device program's fold pass (pf_fold.h).  0 = off, 1 = on (default),
-// 2 = the fold pass alone, without the peepholes after it (its output is still a lowered
-// program, so tests can feed it back in).  pf_batch_create takes the value read at init,
-// pf_device_program reads it on every call.
-// pf_batch_create folds only batches of PF_FOLD_MIN_SETS sets or more.  The walk costs ~19 ns
-// per instruction on the host (corpus batch, 1,023 sets / 507,856 instructions: 2.6 -> 3.9 ms)
-// and pays back over the candidates a set is swept with; a single query's batch is one or two
-// buckets of ~500 instructions searched with early exit, and its upload phase grew from 0.073
-// to 0.083 ms (run-to-run spread 0.001) for no search time back (profiles/r07_fold_ab.md).
-// No program length makes the walk free, so the gate is the batch's set count.
+// PF_DEVICE_FOLD as read at init (pf_devprog.h device_fold_env): what pf_batch_create folds with
 int g_device_fold = 1;
-constexpr size_t PF_FOLD_MIN_SETS = 16;
-int device_fold_env() {
-    const char* e = getenv("PF_DEVICE_FOLD");
-    if (!e || !*e) return 1;
-    const long v = strtol(e, nullptr, 10);
-    return v >= 0 && v <= 2 ? (int)v : 1;
-}
 
 int fail(const char* fmt, ...) {
     char buf[512];
@@ -111,10 +101,7 @@ int fail(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    if (t_defer_err)
-        t_err = buf;
-    else
-        g_err = buf;
+    g_err = buf;
     return -1;
 }
 
@@ -257,23 +244,17 @@ int switch_stream(Dev* D, hipStream_t st) {
     return 0;
 }
 
-// select (and make current) a device: the default one for device < 0
-Dev* use_dev(int device) {
-    if (g_devs.empty()) {
-        fail("pf_init() has not been called");
-        return nullptr;
-    }
-    Dev* D = device < 0 ? g_devs[g_default].get() : find_dev(device);
-    if (!D) {
-        fail("device %d was not initialised by pf_init", device);
-        return nullptr;
-    }
-    hipError_t e = hipSetDevice(D->id);
-    if (e != hipSuccess) {
-        fail("hipSetDevice(%d): %s", D->id, hipGetErrorString(e));
-        return nullptr;
-    }
-    return D;
+// select (and make current) a device: the default one for device < 0.  An error goes to g_err,
+// or to *err for the one caller that does not hold g_mu (pf_batch_create_on)
+Dev* use_dev(int device, std::string* err = nullptr) {
+    std::string e;
+    Dev* D = g_devs.empty() ? nullptr : device < 0 ? g_devs[g_default].get() : find_dev(device);
+    if (g_devs.empty()) e = "pf_init() has not been called";
+    else if (!D) e = errorf("device %d was not initialised by pf_init", device);
+    else if (hipError_t h = hipSetDevice(D->id)) e = errorf("hipSetDevice(%d): %s", D->id, hipGetErrorString(h));
+    if (e.empty()) return D;
+    (err ? *err : g_err) = e;
+    return nullptr;
 }
 
 Batch* as_batch(uint64_t h) { return reinterpret_cast<Batch*>(static_cast<uintptr_t>(h)); }
@@ -453,394 +434,6 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
     return 0;
 }
 
-// The device form of a validated batch (traffic / unit bits already set): a fold pass and
-// semantics-preserving peepholes rewrite the program the kernel runs, never the caller's
-// arrays (the oracles evaluate the program as lowered).  Each set is rewritten in a scratch
-// copy (descriptors may share or reorder code ranges) and appended to code_out; every pass is
-// one forward walk with per-register state.  Shared by pf_batch_create and the host-only test
-// export pf_device_program.
-//  0. fold (pf_fold.h, PF_DEVICE_FOLD): results that are the same for every candidate —
-//     constant operands, x-op-x identities, absorbing and neutral constants, compares and
-//     divisions a value's range decides — become a W_MOV, W_CONST (of the set's pool, or of a
-//     constant of the program's own: OwnConsts below), B_CONST or W_XOR r, r, and what only
-//     they needed is dropped (liveness from the ASSERTs).  The passes below clean up after it (its W_MOVs and W_CONSTs mostly vanish).
-//     aux1 of every dropped instruction, here or below, moves to the next kept one: a wave
-//     leaves a program only at an assert, so `ops` counts what it counted for the lowered
-//     program (the counter contract).
-//  1. ASSERT: folded into the last writer of its B register when that is a compare or bool op
-//     (PF_I_ASSERT) — the conjunction's value does not depend on where the and happens, and
-//     with PF_FLAG_SHORTCIRCUIT an earlier check only exits sooner (round 2 folded it only
-//     into the instruction right before it).
-//  2. W_MOV: a zero-extending move (its source holds a value no wider than the move — values
-//     are kept zero-extended, so the move copies it unchanged) is deleted and the readers of
-//     its destination, up to that register's next write, read the source — provided the
-//     source is not rewritten before the last of them.
-//  3. W_CONST: deleted when its register is read, until its next write, only as the a / b
-//     operand of W-reading instructions (not SPILL or MOV); those take the constant directly
-//     (PF_I_KA / PF_I_KB, the constant index in the register field, traffic bit cleared) and
-//     the kernel reads it with one scalar load.
-//     A constant is folded only when it fits the W_CONST's width: the W_CONST masks its value
-//     at write-back, a folded operand is read raw (ADVICE r4 — the lowering never packs a
-//     wider one, but pf_batch_create trusts nothing the caller packed).
-// consts (n_const x 8 u32, set-relative indices resolved through const_off) may be null: then
-// every constant is taken to fit (pf_device_program's callers that pass none).
-bool const_fits(const uint32_t* consts, size_t n_const, uint32_t idx, uint32_t w) {
-    if (!consts) return true;
-    if (idx >= n_const) return false;
-    const uint32_t* c = consts + 8 * (size_t)idx;
-    for (uint32_t j = 0; j < 8; j++) {
-        const uint32_t lo = 32u * j;
-        const uint32_t keep = w >= lo + 32u ? 0xffffffffu : (w > lo ? (1u << (w - lo)) - 1u : 0u);
-        if (c[j] & ~keep) return false;
-    }
-    return true;
-}
-
-// Constants of the device programs' own (pf_fold.h: a constant result that is neither 0 nor in
-// the set's pool): vals holds 8 u32 each in set order, cnt[s] how many set s has.  Their indices
-// follow the set's own n_const constants (device_pool lays the pool out that way).
-struct OwnConsts {
-    std::vector<uint32_t> vals;
-    std::vector<uint32_t> cnt;
-};
-
-// Sets [s0, s1) of the batch: their device programs appended to code_out, each set's
-// code_off rewritten to its offset in code_out.  own (may be null: pf_device_program, whose
-// result is read against the caller's pool) collects the sets' own constants.
-void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& descs_out, size_t s0, size_t s1,
-                          std::vector<uint32_t>& code_out, const uint32_t* consts, size_t n_const, int fold,
-                          OwnConsts* own = nullptr) {
-    std::vector<uint32_t> P;      // the set being rewritten
-    pf_fold::Scratch fold_scratch;
-    std::vector<uint8_t> drop;
-    struct Pending {              // pass 3: the W_CONST a register holds, and its readers
-        int64_t at = -1;
-        bool ok = true;
-        std::vector<uint32_t> readers;
-    };
-    Pending pend[PF_NW + 1];
-    for (size_t s = s0; s < s1; s++) {
-        pf_set_desc& d = descs_out[s];
-        const uint32_t n = d.n_ins;
-        P.assign(code_fixed + 4 * (size_t)d.code_off, code_fixed + 4 * ((size_t)d.code_off + n));
-        drop.assign(n, 0);
-        auto tr_of = [&](uint32_t i) { return (P[4 * i] >> 18) & 7u; };
-        // ---- 0. constants, identities and dead code
-        if (fold) {
-            const bool pool = consts && (uint64_t)d.const_off + d.n_const <= n_const;
-            // a set without constants has a pool all the same: the empty one
-            const bool own_ok = own && (pool || (d.n_const == 0 && d.const_off <= n_const));
-            const size_t before = own ? own->vals.size() : 0;
-            pf_fold::fold_program(P.data(), n, drop.data(), pool ? consts + 8 * (size_t)d.const_off : nullptr,
-                                  pool ? d.n_const : 0u, fold_scratch, own_ok ? &own->vals : nullptr);
-            if (own) own->cnt[s] = (uint32_t)((own->vals.size() - before) / 8);
-        }
-        // ---- 1. ASSERT -> PF_I_ASSERT on the last writer of its register
-        if (fold != 2) {
-            int64_t last_b[PF_NB];
-            for (int r = 0; r < PF_NB; r++) last_b[r] = -1;
-            for (uint32_t i = 0; i < n; i++) {
-                if (drop[i]) continue;
-                const uint32_t op = P[4 * i] & 0xffu;
-                if (op == PF_ASSERT) {
-                    const int64_t k = last_b[(P[4 * i + 1] >> 8) & 31u];
-                    if (k >= 0) {
-                        const uint32_t unit = pf_op_unit(P[4 * (size_t)k] & 0xffu);
-                        if ((unit == PF_U_CMP || unit == PF_U_BOOL) && !(P[4 * (size_t)k] & PF_I_ASSERT)) {
-                            P[4 * (size_t)k] |= PF_I_ASSERT;
-                            drop[i] = 1;
-                        }
-                    }
-                } else if (PF_OP_WRITES_B(op)) {
-                    last_b[P[4 * i + 1] & 31u] = i;
-                }
-            }
-        }
-        // ---- 2. zero-extending W_MOV -> its readers read the source
-        if (fold != 2) {
-            uint32_t wwidth[PF_NW + 1];  // width of the value each W register holds now
-            for (int r = 0; r <= PF_NW; r++) wwidth[r] = 0xffffffffu;
-            for (uint32_t i = 0; i < n; i++) {
-                if (drop[i]) continue;
-                const uint32_t op = P[4 * i] & 0xffu, tr = tr_of(i), dst = P[4 * i + 1] & 0xffu;
-                const uint32_t w = (P[4 * i] >> 8) & 0x3ffu;
-                if (op != PF_W_MOV) {
-                    if ((tr & PF_TR_WW) && dst <= PF_NW) wwidth[dst] = w;
-                    continue;
-                }
-                const uint32_t src = (P[4 * i + 1] >> 8) & 0xffu;
-                bool ok = src <= PF_NW && dst <= PF_NW && wwidth[src] <= w;
-                uint32_t last = i;
-                if (ok) {
-                    bool src_dead = false;
-                    for (uint32_t j = i + 1; j < n; j++) {
-                        if (drop[j]) continue;
-                        const uint32_t jtr = tr_of(j), jw1 = P[4 * j + 1];
-                        const bool reads = ((jtr & PF_TR_RA) && ((jw1 >> 8) & 0xffu) == dst) ||
-                                           ((jtr & PF_TR_RB) && ((jw1 >> 16) & 0xffu) == dst);
-                        if (reads) {
-                            if (src_dead) { ok = false; break; }
-                            last = j;
-                        }
-                        if ((jtr & PF_TR_WW) && (jw1 & 0xffu) == dst) break;
-                        if ((jtr & PF_TR_WW) && (jw1 & 0xffu) == src) src_dead = true;
-                        if ((P[4 * j] & 0xffu) == PF_END) break;
-                    }
-                }
-                if (!ok) {
-                    if (dst <= PF_NW) wwidth[dst] = w;
-                    continue;
-                }
-                for (uint32_t t = i + 1; t <= last; t++) {
-                    const uint32_t jtr = tr_of(t);
-                    uint32_t& w1 = P[4 * t + 1];
-                    if ((jtr & PF_TR_RA) && ((w1 >> 8) & 0xffu) == dst) w1 = (w1 & ~0xff00u) | (src << 8);
-                    if ((jtr & PF_TR_RB) && ((w1 >> 16) & 0xffu) == dst) w1 = (w1 & ~0xff0000u) | (src << 16);
-                }
-                drop[i] = 1;  // dst keeps its old value, which nothing reads before its next write
-            }
-        }
-        // ---- 3. W_CONST -> constant operands of its readers
-        if (fold != 2) {
-            auto settle = [&](uint32_t r) {
-                Pending& q = pend[r];
-                if (q.at >= 0 && q.ok && !q.readers.empty()) {
-                    const uint32_t k = P[4 * (size_t)q.at + 2];
-                    for (uint32_t t : q.readers) {
-                        uint32_t& w0 = P[4 * t];
-                        uint32_t& w1 = P[4 * t + 1];
-                        const uint32_t jtr = (w0 >> 18) & 7u;
-                        if ((jtr & PF_TR_RA) && ((w1 >> 8) & 0xffu) == r) {
-                            w0 = (w0 & ~(PF_TR_RA << 18)) | PF_I_KA;
-                            w1 = (w1 & ~0xff00u) | (k << 8);
-                        }
-                        if ((jtr & PF_TR_RB) && ((w1 >> 16) & 0xffu) == r) {
-                            w0 = (w0 & ~(PF_TR_RB << 18)) | PF_I_KB;
-                            w1 = (w1 & ~0xff0000u) | (k << 16);
-                        }
-                    }
-                    drop[q.at] = 1;
-                }
-                q.at = -1;
-                q.ok = true;
-                q.readers.clear();
-            };
-            for (uint32_t i = 0; i < n; i++) {
-                if (drop[i]) continue;
-                const uint32_t op = P[4 * i] & 0xffu, tr = tr_of(i), w1 = P[4 * i + 1];
-                const uint32_t ra = (w1 >> 8) & 0xffu, rb = (w1 >> 16) & 0xffu, rd = w1 & 0xffu;
-                if (op == PF_END) break;
-                // reads first (an instruction may read and rewrite the same register)
-                for (int side = 0; side < 2; side++) {
-                    const uint32_t r = side ? rb : ra;
-                    if (!(tr & (side ? PF_TR_RB : PF_TR_RA)) || r > PF_NW || pend[r].at < 0) continue;
-                    if (side && (tr & PF_TR_RA) && ra == r) continue;  // the same register twice
-                    if (op == PF_W_SPILL || op == PF_W_MOV) pend[r].ok = false;
-                    else pend[r].readers.push_back(i);
-                }
-                if ((tr & PF_TR_WW) && rd <= PF_NW) {
-                    settle(rd);
-                    // (a constant of the program's own is below 2^w of the instruction it replaced)
-                    if (op == PF_W_CONST && P[4 * i + 2] <= 0xffu &&
-                        ((own && P[4 * i + 2] >= d.n_const) ||
-                         const_fits(consts, n_const, d.const_off + P[4 * i + 2], (P[4 * i] >> 8) & 0x3ffu)))
-                        pend[rd].at = i;
-                }
-            }
-            for (uint32_t r = 0; r <= PF_NW; r++) settle(r);
-        }
-        // ---- 4. spill slots -> LDS entries 1..3 of EXP's window table (PF_SPILL_LDS)
-        // A segment is a SPILL of slot k and the FILLs of k before its next SPILL.  One whose
-        // range holds no W_EXP takes entry 2 or 3 when free (entry 1 too if no B_UMUL_NOOVF
-        // runs in it): the value never touches scratch.  Entries are handed out in program
-        // order; a segment without a FILL stays (a dead store costs nothing more).
-        if (fold != 2) {
-            struct Seg {
-                uint32_t spill, last;
-                std::vector<uint32_t> fills;
-            };
-            std::vector<Seg> segs;
-            int64_t open[PF_MAX_SPILL];
-            for (int k = 0; k < PF_MAX_SPILL; k++) open[k] = -1;
-            std::vector<uint32_t> exp_at, umul_at;
-            for (uint32_t i = 0; i < n; i++) {
-                if (drop[i]) continue;
-                const uint32_t op = P[4 * i] & 0xffu, k = P[4 * i + 2] & (PF_MAX_SPILL - 1u);
-                if (op == PF_END) break;
-                if (op == PF_W_EXP) exp_at.push_back(i);
-                if (op == PF_B_UMUL_NOOVF) umul_at.push_back(i);
-                if (op == PF_W_SPILL || op == PF_B_SPILL) {
-                    open[k] = (int64_t)segs.size();
-                    segs.push_back(Seg{i, i, {}});
-                } else if ((op == PF_W_FILL || op == PF_B_FILL) && open[k] >= 0) {
-                    Seg& g = segs[(size_t)open[k]];
-                    g.fills.push_back(i);
-                    g.last = i;
-                }
-            }
-            auto any_in = [](const std::vector<uint32_t>& at, uint32_t lo, uint32_t hi) {
-                const auto it = std::upper_bound(at.begin(), at.end(), lo);
-                return it != at.end() && *it < hi;
-            };
-            int64_t busy_until[4] = {-1, -1, -1, -1};
-            static const uint32_t order[3] = {2u, 3u, 1u};
-            for (const Seg& g : segs) {
-                if (g.fills.empty() || any_in(exp_at, g.spill, g.last)) continue;
-                const bool umul = any_in(umul_at, g.spill, g.last);
-                for (uint32_t e : order) {
-                    if ((e == 1u && umul) || busy_until[e] >= (int64_t)g.spill) continue;
-                    busy_until[e] = g.last;
-                    P[4 * (size_t)g.spill + 2] = PF_SPILL_LDS | e;
-                    for (uint32_t f : g.fills) P[4 * (size_t)f + 2] = PF_SPILL_LDS | e;
-                    break;
-                }
-            }
-        }
-        // ---- 5. back-to-back forwarding: an instruction reading the W register the kept
-        // instruction right before it wrote takes that result directly (PF_I_FA / PF_I_FB,
-        // traffic bit cleared), and the writer skips its write-back (PF_TR_WW cleared) when
-        // no later instruction reads the register before its next write
-        if (fold != 2) {
-            int64_t prev = -1;
-            for (uint32_t q = 0; q < n; q++) {
-                if (drop[q]) continue;
-                const int64_t p = prev;
-                prev = q;
-                uint32_t& qw0 = P[4 * q];
-                const uint32_t qop = qw0 & 0xffu;
-                if (qop == PF_END) break;
-                if (p < 0) continue;
-                uint32_t& pw0 = P[4 * (size_t)p];
-                const uint32_t ptr = (pw0 >> 18) & 7u, pd = P[4 * (size_t)p + 1] & 0xffu;
-                if (!(ptr & PF_TR_WW) || PF_OP_WRITES_B(pw0 & 0xffu) || pd > PF_NW) continue;
-                const uint32_t qtr = (qw0 >> 18) & 7u, qw1 = P[4 * q + 1];
-                const bool fa = (qtr & PF_TR_RA) && ((qw1 >> 8) & 0xffu) == pd;
-                const bool fb = (qtr & PF_TR_RB) && ((qw1 >> 16) & 0xffu) == pd;
-                if (!fa && !fb) continue;
-                qw0 &= ~(((fa ? PF_TR_RA : 0u) | (fb ? PF_TR_RB : 0u)) << 18);
-                qw0 |= (fa ? PF_I_FA : 0u) | (fb ? PF_I_FB : 0u);
-                bool live = false;
-                if (!((qtr & PF_TR_WW) && (qw1 & 0xffu) == pd)) {
-                    for (uint32_t r = q + 1; r < n && !live; r++) {
-                        if (drop[r]) continue;
-                        const uint32_t rw0 = P[4 * r], rw1 = P[4 * r + 1], rtr = (rw0 >> 18) & 7u;
-                        if ((rw0 & 0xffu) == PF_END) break;
-                        live = ((rtr & PF_TR_RA) && ((rw1 >> 8) & 0xffu) == pd) ||
-                               ((rtr & PF_TR_RB) && ((rw1 >> 16) & 0xffu) == pd);
-                        if ((rtr & PF_TR_WW) && (rw1 & 0xffu) == pd) break;
-                    }
-                }
-                if (!live) pw0 &= ~(PF_TR_WW << 18);
-            }
-        }
-        const size_t first = code_out.size() / 4;
-        size_t kept = 0;
-        for (uint32_t i = 0; i < n; i++) kept += !drop[i];
-        code_out.resize(4 * (first + kept));
-        uint32_t* o = code_out.data() + 4 * first;
-        uint32_t carry = 0;  // aux1 of the dropped instructions since the last kept one
-        for (uint32_t i = 0; i < n; i++) {
-            if (drop[i]) {
-                carry += P[4 * (size_t)i + 3];
-                continue;
-            }
-            memcpy(o, P.data() + 4 * (size_t)i, 16);
-            o[3] += carry;
-            carry = 0;
-            o += 4;
-        }
-        d.code_off = (uint32_t)first;
-        d.n_ins = (uint32_t)kept;
-    }
-}
-
-// Host threads for a batch's preparation and the set ranges they take (about equal
-// instruction counts): one for small batches (a single query's), up to 8 for large ones.
-std::vector<size_t> prep_ranges(const pf_set_desc* descs, size_t n_sets, size_t n_ins) {
-    size_t nt = 1;
-    if (n_sets >= 64 && n_ins >= (1u << 15)) {
-        // hardware_concurrency reads sysfs: once per process, and not on a small batch's path
-        static const size_t hw = std::max<size_t>(1, std::thread::hardware_concurrency());
-        nt = std::min<size_t>({8, hw, n_sets / 32});
-    }
-    std::vector<size_t> cut(nt + 1, n_sets);
-    cut[0] = 0;
-    uint64_t total = 0, acc = 0;
-    for (size_t s = 0; s < n_sets; s++) total += descs[s].n_ins;
-    size_t t = 1;
-    for (size_t s = 0; s < n_sets && t < nt; s++) {
-        acc += descs[s].n_ins;
-        if (acc * nt >= total * t) cut[t++] = s + 1;
-    }
-    return cut;
-}
-
-// fn(t) for t in [0, n) on the caller and n - 1 spawned threads
-template <typename F>
-void run_ranges(size_t n, F&& fn) {
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < n; t++) th.emplace_back(fn, t);
-    fn(0);
-    for (auto& x : th) x.join();
-}
-
-// The device program of every set: each range of `cut` rewritten into its own buffer (on its
-// own thread), then concatenated in set order — the program one pass over all sets gives.
-// pool_out (may be null: no constants of the programs' own) receives the device constant pool
-// when it differs from the caller's (else it is left empty): the caller's n_const constants verbatim, then, for every set that gained constants of its
-// own, that set's constants again followed by the new ones, with the set's const_off pointing
-// there.  n_const of the descriptors stays the caller's count — the candidate generator
-// draws from [const_off, const_off + n_const) and sees the constants it saw before — and a set
-// without new constants keeps its range.
-void device_program(const uint32_t* code_fixed, size_t n_fixed, std::vector<pf_set_desc>& descs_out,
-                    const std::vector<size_t>& cut, std::vector<uint32_t>& code_out, const uint32_t* consts,
-                    size_t n_const, int fold, std::vector<uint32_t>* pool_out = nullptr) {
-    const size_t nt = cut.size() - 1, n_sets = descs_out.size();
-    code_out.clear();
-    const bool owning = pool_out && fold;
-    std::vector<OwnConsts> own(owning ? nt : 0);
-    for (OwnConsts& o : own) o.cnt.assign(n_sets, 0);
-    if (nt == 1) {
-        code_out.reserve(n_fixed);
-        device_program_range(code_fixed, descs_out, 0, n_sets, code_out, consts, n_const, fold,
-                             owning ? &own[0] : nullptr);
-    } else {
-        std::vector<std::vector<uint32_t>> outs(nt);
-        run_ranges(nt, [&](size_t t) {
-            device_program_range(code_fixed, descs_out, cut[t], cut[t + 1], outs[t], consts, n_const, fold,
-                                 owning ? &own[t] : nullptr);
-        });
-        size_t total = 0;
-        for (const auto& o : outs) total += o.size();
-        code_out.reserve(total);
-        for (size_t t = 0; t < nt; t++) {
-            const uint32_t base = (uint32_t)(code_out.size() / 4);
-            for (size_t s = cut[t]; s < cut[t + 1]; s++) descs_out[s].code_off += base;
-            code_out.insert(code_out.end(), outs[t].begin(), outs[t].end());
-        }
-    }
-    if (!pool_out) return;
-    pool_out->clear();
-    size_t n_own = 0;
-    for (const OwnConsts& o : own) n_own += o.vals.size();
-    if (!n_own) return;  // left empty: the device pool is the caller's, no copy
-    if (consts) pool_out->assign(consts, consts + 8 * n_const);
-    for (size_t t = 0; t < own.size(); t++) {
-        const uint32_t* v = own[t].vals.data();
-        for (size_t s = cut[t]; s < cut[t + 1]; s++) {
-            const uint32_t k = own[t].cnt[s];
-            if (!k) continue;
-            pf_set_desc& d = descs_out[s];
-            const uint32_t at = (uint32_t)(pool_out->size() / 8);
-            if (d.n_const) pool_out->insert(pool_out->end(), consts + 8 * (size_t)d.const_off,
-                                            consts + 8 * ((size_t)d.const_off + d.n_const));
-            pool_out->insert(pool_out->end(), v, v + 8 * (size_t)k);
-            v += 8 * (size_t)k;
-            d.const_off = at;
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -854,12 +447,7 @@ int pf_version(void) { return 2; }
 int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
                       const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
                       pf_set_desc* descs_out) {
-    std::vector<uint32_t> fixed(code, code + 4 * n_ins);
-    for (size_t i = 0; i < n_ins; i++) {
-        uint32_t* I = fixed.data() + 4 * i;
-        const uint32_t op = I[0] & 0xffu;
-        I[0] = (I[0] & 0x3ffffu) | (pf_op_traffic(op) << 18) | (pf_op_unit(op) << 21);
-    }
+    const std::vector<uint32_t> fixed = stamped(code, n_ins);
     std::vector<pf_set_desc> d(descs, descs + n_sets);
     std::vector<uint32_t> out;
     device_program(fixed.data(), fixed.size(), d, prep_ranges(descs, n_sets, n_ins), out, consts, n_const,
@@ -879,12 +467,7 @@ int pf_device_program(const uint32_t* code, size_t n_ins, const uint32_t* consts
 int pf_device_batch(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
                     const pf_set_desc* descs, size_t n_sets, uint32_t* code_out, size_t* n_ins_out,
                     pf_set_desc* descs_out, uint32_t* consts_out, size_t consts_cap, size_t* n_const_out) {
-    std::vector<uint32_t> fixed(code, code + 4 * n_ins);
-    for (size_t i = 0; i < n_ins; i++) {
-        uint32_t* I = fixed.data() + 4 * i;
-        const uint32_t op = I[0] & 0xffu;
-        I[0] = (I[0] & 0x3ffffu) | (pf_op_traffic(op) << 18) | (pf_op_unit(op) << 21);
-    }
+    const std::vector<uint32_t> fixed = stamped(code, n_ins);
     std::vector<pf_set_desc> d(descs, descs + n_sets);
     std::vector<uint32_t> out, pool;
     device_program(fixed.data(), fixed.size(), d, prep_ranges(descs, n_sets, n_ins), out, consts, n_const,
@@ -892,10 +475,8 @@ int pf_device_batch(const uint32_t* code, size_t n_ins, const uint32_t* consts, 
     const uint32_t* pc = pool.empty() ? consts : pool.data();
     const size_t np = pool.empty() ? n_const : pool.size() / 8;
     *n_const_out = np;
-    if (np > consts_cap) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        return fail("pf_device_batch: the device pool holds %zu constants, room for %zu", np, consts_cap);
-    }
+    if (np > consts_cap)
+        return set_err(errorf("pf_device_batch: the device pool holds %zu constants, room for %zu", np, consts_cap));
     memcpy(code_out, out.data(), out.size() * 4);
     *n_ins_out = out.size() / 4;
     memcpy(descs_out, d.data(), n_sets * sizeof(pf_set_desc));
@@ -1046,129 +627,6 @@ int pf_shutdown(void) {
     return 0;
 }
 
-// Set s: its ranges, operands and schema checked against the batch, and its instructions
-// copied into fixed[] (the set's own range) with the traffic / unit bits recomputed and
-// register def-before-use checked; wide[s] set.  0 or fail().
-static int check_set(size_t s, const uint32_t* code, size_t n_ins, size_t n_const, const uint32_t* schema,
-                     size_t n_vars, size_t n_parents, const pf_set_desc* descs, uint32_t* fixed, uint8_t* wide) {
-    {
-        const pf_set_desc& d = descs[s];
-        if ((uint64_t)d.code_off + d.n_ins > n_ins || d.n_ins == 0)
-            return fail("set %zu: code range [%u,+%u) outside %zu instructions", s, d.code_off, d.n_ins, n_ins);
-        if ((uint64_t)d.const_off + d.n_const > n_const)
-            return fail("set %zu: constant range outside pool", s);
-        if ((uint64_t)d.var_off + d.n_vars > n_vars) return fail("set %zu: schema range outside", s);
-        if ((code[4 * ((size_t)d.code_off + d.n_ins - 1)] & 0xffu) != PF_END)
-            return fail("set %zu: program does not end with PF_END", s);
-        for (uint32_t i = 0; i < d.n_ins; i++) {
-            const uint32_t* I = code + 4 * ((size_t)d.code_off + i);
-            uint32_t op = I[0] & 0xffu, w = (I[0] >> 8) & 0x3ffu;
-            if (op != PF_END && (w == 0 || w > PF_MAX_WIDTH))
-                return fail("set %zu ins %u: width %u out of range", s, i, w);
-            if ((op == PF_W_VAR || op == PF_B_VAR) && I[2] >= d.n_vars)
-                return fail("set %zu ins %u: variable %u >= %u", s, i, I[2], d.n_vars);
-            if (op == PF_W_CONST && I[2] >= d.n_const)
-                return fail("set %zu ins %u: constant %u >= %u", s, i, I[2], d.n_const);
-        }
-        for (uint32_t v = 0; v < d.n_vars; v++) {
-            const uint32_t* sc = schema + 4 * ((size_t)d.var_off + v);
-            uint32_t kind = sc[0] & 0xffu, w = (sc[0] >> 8) & 0x3ffu;
-            if (w == 0 || w > PF_MAX_WIDTH) return fail("set %zu var %u: width %u", s, v, w);
-            if (sc[3] != PF_NO_PARENT && sc[3] >= n_parents) return fail("set %zu var %u: parent slot", s, v);
-            if (kind == PF_VK_KECCAK && sc[1] >= d.n_const) return fail("set %zu var %u: keccak base", s, v);
-            if (kind == PF_VK_ACTOR && (sc[2] > 4 || sc[1] + sc[2] > d.n_const))
-                return fail("set %zu var %u: actor table", s, v);
-            if (kind == PF_VK_CDBYTE && ((sc[1] & 0xffu) > 248u || (sc[1] & 7u) ||
-                                         (sc[1] >> 20) + ((sc[1] >> 8) & 0xfffu) > d.n_const))
-                return fail("set %zu var %u: calldata word constants", s, v);
-        }
-    }
-    // traffic bits and register def-before-use, recomputed here so the kernel can trust
-    // them whatever the caller packed (w0 bits 18..23)
-    {
-        const pf_set_desc& d = descs[s];
-        memcpy(fixed + 4 * (size_t)d.code_off, code + 4 * (size_t)d.code_off, 16 * (size_t)d.n_ins);
-        uint32_t wdef = 0u, bdef = 0u, max_wreg = 0u;
-        uint64_t sdef = 0ull;
-        for (uint32_t i = 0; i < d.n_ins; i++) {
-            uint32_t* I = fixed + 4 * ((size_t)d.code_off + i);
-            const uint32_t op = I[0] & 0xffu, tr = pf_op_traffic(op);
-            I[0] = (I[0] & 0x3ffffu) | (tr << 18) | (pf_op_unit(op) << 21);
-            const uint32_t rd = I[1] & 0xffu, ra = (I[1] >> 8) & 0xffu, rb = (I[1] >> 16) & 0xffu,
-                           rc = (I[1] >> 24) & 0xffu;
-            if ((tr & PF_TR_WW) && rd >= PF_NW) return fail("set %zu ins %u: W dst %u", s, i, rd);
-            if (((tr & PF_TR_RA) && (ra >= PF_NW || !(wdef >> ra & 1u))) ||
-                ((tr & PF_TR_RB) && (rb >= PF_NW || !(wdef >> rb & 1u))))
-                return fail("set %zu ins %u: W register read before write", s, i);
-            const bool bres = PF_OP_WRITES_B(op);
-            const bool breads_ab = op >= PF_B_AND && op <= PF_B_XOR;
-            if ((breads_ab && (!(bdef >> (ra & 31u) & 1u) || !(bdef >> (rb & 31u) & 1u))) ||
-                ((op == PF_B_NOT || op == PF_ASSERT || op == PF_B_SPILL) && !(bdef >> (ra & 31u) & 1u)) ||
-                ((op == PF_W_ITE || op == PF_B_ITE) && !(bdef >> (rc & 31u) & 1u)) ||
-                (op == PF_B_ITE && (!(bdef >> (ra & 31u) & 1u) || !(bdef >> (rb & 31u) & 1u))))
-                return fail("set %zu ins %u: B register read before write", s, i);
-            if ((op == PF_W_SPILL || op == PF_W_FILL || op == PF_B_SPILL || op == PF_B_FILL) &&
-                I[2] >= PF_MAX_SPILL)
-                return fail("set %zu ins %u: spill slot %u >= %d", s, i, I[2], PF_MAX_SPILL);
-            if (op == PF_W_SPILL || op == PF_B_SPILL) sdef |= 1ull << I[2];
-            if ((op == PF_W_FILL || op == PF_B_FILL) && !(sdef >> I[2] & 1ull))
-                return fail("set %zu ins %u: spill slot %u filled before it was spilled", s, i, I[2]);
-            if (tr & PF_TR_WW) {
-                wdef |= 1u << rd;
-                max_wreg = std::max(max_wreg, rd);
-            }
-            if (i + 1 == d.n_ins) wide[s] = max_wreg >= PF_NW_NARROW;
-            if (bres) bdef |= 1u << (rd & 31u);
-        }
-    }
-    return 0;
-}
-
-// Host-side checks of packed programs and their device form (pf_batch_create and
-// pf_eval_program): every kernel index is derived from these, so nothing the caller packed is
-// trusted.  Fills the device program and the device constant pool (device_program; fold: the
-// PF_DEVICE_FOLD value, applied to batches of PF_FOLD_MIN_SETS sets or more), the per-set wide
-// flags and the largest variable count; returns 0 or fail().  A large batch (the corpus pass: 1,023 sets, 376k
-// instructions, ~10 ms on one host thread) is checked and rewritten in set ranges on host
-// threads, each range's device program appended to its own buffer, then concatenated in set
-// order — the same program as the serial pass; a range that fails sends the whole batch
-// through the serial pass, so the error reported is the first set's, as before.
-static int prepare_program(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
-                           const uint32_t* schema, size_t n_vars, size_t n_parents, const pf_set_desc* descs,
-                           size_t n_sets, std::vector<uint32_t>& code_out, std::vector<pf_set_desc>& descs_out,
-                           std::vector<uint32_t>& pool_out, std::vector<uint8_t>& wide, uint32_t& max_vars,
-                           int fold) {
-    max_vars = 0;
-    for (size_t s = 0; s < n_sets; s++) max_vars = std::max(max_vars, descs[s].n_vars);
-    std::vector<uint32_t> code_fixed(4 * n_ins);
-    wide.assign(n_sets, 0);
-    descs_out.assign(descs, descs + n_sets);
-    const std::vector<size_t> cut = prep_ranges(descs, n_sets, n_ins);
-    const size_t nt = cut.size() - 1;
-    bool bad = false;
-    if (nt > 1) {
-        std::vector<uint8_t> bad_t(nt, 0);
-        const bool defer = t_defer_err;
-        run_ranges(nt, [&](size_t t) {
-            t_defer_err = true;  // a failing range's message stays on its thread: the serial pass reports
-            for (size_t s = cut[t]; s < cut[t + 1] && !bad_t[t]; s++)
-                bad_t[t] = check_set(s, code, n_ins, n_const, schema, n_vars, n_parents, descs, code_fixed.data(),
-                                     wide.data()) != 0;
-        });
-        t_defer_err = defer;
-        bad = std::find(bad_t.begin(), bad_t.end(), (uint8_t)1) != bad_t.end();
-    }
-    if (nt == 1 || bad) {
-        for (size_t s = 0; s < n_sets; s++)
-            if (check_set(s, code, n_ins, n_const, schema, n_vars, n_parents, descs, code_fixed.data(),
-                          wide.data()))
-                return -1;
-    }
-    device_program(code_fixed.data(), code_fixed.size(), descs_out, cut, code_out, consts, n_const,
-                   n_sets >= PF_FOLD_MIN_SETS ? fold : 0, &pool_out);
-    return 0;
-}
-
 int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uint32_t* consts,
                        size_t n_const, const uint32_t* schema, size_t n_vars,
                        const uint32_t* parents, size_t n_parents, const pf_set_desc* descs,
@@ -1177,53 +635,20 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     // no library state and runs before the lock: a caller uploading the next batch from
     // another thread (tools/full_pass.py) overlaps it with a search in progress, which holds
     // the lock until its results are back.
-    std::vector<uint32_t> code_out;
-    std::vector<pf_set_desc> descs_out;
-    std::vector<uint32_t> pool_out;
-    std::vector<uint8_t> wide;
-    uint32_t max_vars = 0;
-    t_defer_err = true;
-    const int prc = prepare_program(code, n_ins, consts, n_const, schema, n_vars, n_parents, descs, n_sets,
-                                    code_out, descs_out, pool_out, wide, max_vars, g_device_fold);
-    t_defer_err = false;
-    if (prc) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        g_err = t_err;
-        return -1;
-    }
-    code = code_out.data();
-    n_ins = code_out.size() / 4;
-    descs = descs_out.data();
+    Prepared pp = prepare_program(code, n_ins, consts, n_const, schema, n_vars, n_parents, descs, n_sets,
+                                  g_device_fold);
+    if (!pp.err.empty()) return set_err(pp.err);
+    code = pp.code.data();
+    n_ins = pp.code.size() / 4;
+    descs = pp.descs.data();
     // the device pool: the caller's constants, then the sets' own (device_program); every
     // const_off below and on the device is an offset into it
-    if (!pool_out.empty()) {
-        consts = pool_out.data();
-        n_const = pool_out.size() / 8;
+    if (!pp.pool.empty()) {
+        consts = pp.pool.data();
+        n_const = pp.pool.size() / 8;
     }
-    // Longest-first wave order: waves are dispatched in index order, so mapping the first
-    // waves to the most expensive sets leaves the cheap ones for the last, partly filled
-    // round.  Weights are measured SIMD cycles per instruction relative to a cheap op
-    // (EXP ~7.1k, a division ~2.6k, MUL ~750, cheap ~650).  8-register sets
-    // come first (their launch precedes the 16-register one's).
-    std::vector<uint64_t> cost(n_sets, 0);
-    std::vector<uint32_t> sites(n_sets, 0);  // assert sites (the climb contract's witness score)
-    for (size_t s = 0; s < n_sets; ++s) {
-        const uint4* I = reinterpret_cast<const uint4*>(code) + descs[s].code_off;
-        uint64_t c = 0;
-        uint32_t ns = 0;
-        for (uint32_t i = 0; i < descs[s].n_ins; ++i) {
-            const uint32_t op = I[i].x & 0xffu;
-            c += op == PF_W_EXP ? 110u : op == PF_W_MUL ? 12u : pf_op_unit(op) == PF_U_DIV ? 40u : 10u;
-            ns += (uint32_t)(op == PF_ASSERT) | (uint32_t)((I[i].x & PF_I_ASSERT) != 0u);
-        }
-        cost[s] = c;
-        sites[s] = ns;
-    }
-    std::vector<uint32_t> order(n_sets);
-    for (size_t s = 0; s < n_sets; ++s) order[s] = (uint32_t)s;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return wide[a] != wide[b] ? wide[a] < wide[b] : cost[a] > cost[b];
-    });
+    // the search kernels' wave order (narrow sets first, then longest first) and the assert sites
+    WaveOrder wo = wave_order(code, descs, n_sets, pp.wide);
 
     // One device block, one copy: [code | consts + one zero entry | schema | parents | descs |
     // order | scratch | found], each region 256-byte aligned (found[] right after the scratch's
@@ -1252,30 +677,24 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         put(o_schema, schema, n_vars * 16);
         put(o_par, parents, n_parents * 32);
         put(o_desc, descs, n_sets * sizeof(pf_set_desc));
-        put(o_order, order.data(), n_sets * 4);
+        put(o_order, wo.order.data(), n_sets * 4);
     };
 
     // No g_mu from here on either: the device lookup holds g_devs_mu (pf_init and
     // pf_init_contexts insert under it; the Dev objects themselves never move), the block comes
-    // from the pool under its own lock, errors go through t_err.
+    // from the pool under its own lock, errors go through set_err.
     Batch* B = nullptr;
     int dev_id = -1;
     hipStream_t ups = nullptr;
-    auto report = [](int rc) {
-        t_defer_err = false;
-        std::lock_guard<std::mutex> lk(g_mu);
-        g_err = t_err;
-        return rc;
-    };
-    t_defer_err = true;
     {
         Dev* Dv = nullptr;
+        std::string dev_err;
         {
             std::lock_guard<std::mutex> dk(g_devs_mu);
-            Dv = use_dev(device);
+            Dv = use_dev(device, &dev_err);
         }
-        if (!Dv) return report(-1);
-        if (!handle_out) return report(fail("pf_batch_create: null handle_out"));
+        if (!Dv) return set_err(dev_err);
+        if (!handle_out) return set_err("pf_batch_create: null handle_out");
         B = new Batch();
         B->device = Dv->key;
         B->n_ins = n_ins;
@@ -1283,20 +702,20 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         B->n_vars = n_vars;
         B->n_parents = n_parents;
         B->n_sets = n_sets;
-        B->max_vars = max_vars;
-        B->n_narrow = (size_t)std::count(wide.begin(), wide.end(), (uint8_t)0);
+        B->max_vars = pp.max_vars;
+        B->n_narrow = (size_t)std::count(pp.wide.begin(), pp.wide.end(), (uint8_t)0);
         // a set without variables counts as parented: its every candidate is candidate 0 (a
         // single query's ground keccak bucket left every such batch without the probe launch)
         B->all_parented = std::all_of(descs, descs + n_sets, [](const pf_set_desc& d) {
             return d.parent_off != PF_NO_PARENT || d.n_vars == 0;
         });
         B->h_descs.assign(descs, descs + n_sets);
-        B->h_wide = wide;
-        B->h_sites = std::move(sites);
+        B->h_wide = std::move(pp.wide);
+        B->h_sites = std::move(wo.sites);
         B->d_mem = pool_acquire(Dv, total, &B->mem_cap);
         if (!B->d_mem) {
             delete B;
-            return report(fail("pf_batch_create: hipMalloc(%zu) failed", total));
+            return set_err(errorf("pf_batch_create: hipMalloc(%zu) failed", total));
         }
         uint8_t* base = static_cast<uint8_t*>(B->d_mem);
         B->d_code = reinterpret_cast<uint4*>(base + o_code);
@@ -1308,14 +727,12 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         B->d_found = reinterpret_cast<uint32_t*>(base + o_found);
         B->d_scratch = reinterpret_cast<uint32_t*>(base + o_scr);
         if (event_acquire(Dv, &B->ev0) != hipSuccess || event_acquire(Dv, &B->ev1) != hipSuccess) {
-            const int rc = fail("pf_batch_create: hipEventCreate failed");
             release_batch(Dv, B);
-            return report(rc);
+            return set_err("pf_batch_create: hipEventCreate failed");
         }
         dev_id = Dv->id;
         ups = Dv->up_stream;
     }
-    t_defer_err = false;
     // the copy itself outside g_mu, on the device's upload stream through the upload staging
     // buffer (a search holding g_mu meanwhile runs on the library stream)
     bool ok = true;
@@ -1336,12 +753,10 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     if (!ok) {
         // the copy may still be in flight: drain the device and free the block rather than
         // pool it (the next pool_acquire would hand out memory still being written)
-        t_defer_err = true;
-        const int rc = fail("pf_batch_create: hipMemcpy of %zu bytes failed", o_scr);
         if (hipDeviceSynchronize() == hipSuccess) hipFree(B->d_mem);
         B->d_mem = nullptr;
         delete B;
-        return report(rc);
+        return set_err(errorf("pf_batch_create: hipMemcpy of %zu bytes failed", o_scr));
     }
     *handle_out = (uint64_t)(uintptr_t)B;
     return 0;
@@ -1724,17 +1139,14 @@ static int eval_programs(const char* who, int device, const uint32_t* code, size
     if (n_cand == 0 || n_sets == 0) return 0;
     if (!code || !sat_out || !descs || (n_vars && !soa)) return fail("%s: null argument", who);
     if (n_sets > 65535) return fail("%s: %zu programs (at most 65535)", who, n_sets);
-    std::vector<uint32_t> code_out;
-    std::vector<pf_set_desc> descs_out;
-    std::vector<uint32_t> pool_out;
-    std::vector<uint8_t> wide;
-    uint32_t max_vars = 0;
-    if (prepare_program(code, n_ins, consts, n_const, schema, n_vars, 0, descs, n_sets, code_out, descs_out,
-                        pool_out, wide, max_vars, g_device_fold))
-        return -1;
-    if (!pool_out.empty()) {  // the device pool (device_program): descs_out index into it
-        consts = pool_out.data();
-        n_const = pool_out.size() / 8;
+    // (under g_mu, as every caller of this is)
+    const Prepared pp = prepare_program(code, n_ins, consts, n_const, schema, n_vars, 0, descs, n_sets, g_device_fold);
+    if (!pp.err.empty()) return fail("%s", pp.err.c_str());
+    const std::vector<uint32_t>& code_out = pp.code;
+    const std::vector<pf_set_desc>& descs_out = pp.descs;
+    if (!pp.pool.empty()) {  // the device pool (device_program): descs_out index into it
+        consts = pp.pool.data();
+        n_const = pp.pool.size() / 8;
     }
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t nv = std::max<size_t>(n_vars, 1), n_dev = code_out.size() / 4, n_out = n_sets * (size_t)n_cand;

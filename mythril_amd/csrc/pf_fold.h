@@ -1,6 +1,6 @@
 /*
  * pf_fold.h — constant folding, x-op-x identities and dead-code removal over one set's lowered
- * program, the first of pf_batch_create's device-program rewrites (pathfeas.hip
+ * program, the first of pf_batch_create's device-program rewrites (pf_devprog.h
  * device_program_range; DESIGN.md §3 "device program rewrites").  Host C++ only.
  *
  * A forward walk keeps, per W register, B register and spill slot, what is known of the value
@@ -121,9 +121,7 @@ struct Scratch {
     }
 };
 
-inline uint32_t mk_w0(uint32_t op, uint32_t w) {
-    return op | (w << 8) | (pf_op_traffic(op) << 18) | (pf_op_unit(op) << 21);
-}
+inline uint32_t mk_w0(uint32_t op, uint32_t w) { return pf_ins_stamp(op | (w << 8)); }
 
 inline bool is_wbin(uint32_t op) {
     return (op >= PF_W_ADD && op <= PF_W_XOR) || (op >= PF_W_SHL && op <= PF_W_EXP);
@@ -177,11 +175,11 @@ inline int range_cmp(uint32_t op, bool x_left, uint32_t p, const U& c, uint32_t 
 // The pass can reason about the program: it ends with its only END, every opcode is known,
 // every register, slot and width is in range, and no device flag is set yet.
 inline bool well_formed(const uint32_t* P, uint32_t n) {
-    if (n == 0 || (P[4 * (size_t)(n - 1)] & 0xffu) != PF_END) return false;
+    if (n == 0 || pf_ins_op(P[4 * (size_t)(n - 1)]) != PF_END) return false;
     for (uint32_t i = 0; i + 1 < n; i++) {
         const uint32_t w0 = P[4 * (size_t)i], w1 = P[4 * (size_t)i + 1], aux0 = P[4 * (size_t)i + 2];
-        const uint32_t op = w0 & 0xffu, w = (w0 >> 8) & 0x3ffu, tr = pf_op_traffic(op);
-        const uint32_t d = w1 & 0xffu, a = (w1 >> 8) & 0xffu, b = (w1 >> 16) & 0xffu, c = w1 >> 24;
+        const uint32_t op = pf_ins_op(w0), w = pf_ins_width(w0), tr = pf_op_traffic(op);
+        const uint32_t d = pf_ins_dst(w1), a = pf_ins_a(w1), b = pf_ins_b(w1), c = pf_ins_c(w1);
         if (w0 >> 24) return false;
         if (op == PF_END || w < 1 || w > PF_MAX_WIDTH) return false;
         const bool known = (op >= PF_W_CONST && op <= PF_W_FILL) || (op >= PF_B_CONST && op <= PF_B_SPILL) ||
@@ -214,7 +212,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
     // uniform shortcuts of the divider and of EXP, and folding would test the host instead.
     bool ground = true;
     for (uint32_t i = 0; i + 1 < n && ground; i++) {
-        const uint32_t op = P[4 * (size_t)i] & 0xffu;
+        const uint32_t op = pf_ins_op(P[4 * (size_t)i]);
         ground = op != PF_W_VAR && op != PF_B_VAR;
     }
     if (ground) return;
@@ -254,8 +252,8 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
     // ---- forward: what every result is, and the rewrites that need no liveness
     for (uint32_t i = 0; i + 1 < n; i++) {
         uint32_t* I = P + 4 * (size_t)i;
-        const uint32_t op = I[0] & 0xffu, w = (I[0] >> 8) & 0x3ffu, aux0 = I[2];
-        const uint32_t d = I[1] & 0xffu, a = (I[1] >> 8) & 0xffu, b = (I[1] >> 16) & 0xffu, c = I[1] >> 24;
+        const uint32_t op = pf_ins_op(I[0]), w = pf_ins_width(I[0]), aux0 = I[2];
+        const uint32_t d = pf_ins_dst(I[1]), a = pf_ins_a(I[1]), b = pf_ins_b(I[1]), c = pf_ins_c(I[1]);
         const uint32_t opw = I[0] & 0x3ffffu;
         T.written[i] = written;
 
@@ -523,8 +521,8 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
     for (uint32_t i = n - 1; i-- > 0;) {
         if (drop[i]) continue;
         uint32_t* I = P + 4 * (size_t)i;
-        uint32_t op = I[0] & 0xffu;
-        const uint32_t w = (I[0] >> 8) & 0x3ffu, d = I[1] & 0xffu;
+        uint32_t op = pf_ins_op(I[0]);
+        const uint32_t w = pf_ins_width(I[0]), d = pf_ins_dst(I[1]);
         bool keep = true;
         if (op == PF_W_SPILL || op == PF_B_SPILL) {
             keep = (live_s >> I[2]) & 1u;
@@ -553,7 +551,7 @@ inline void fold_program(uint32_t* P, uint32_t n, uint8_t* drop, const uint32_t*
             }
         }
         const uint32_t tr = pf_op_traffic(op);
-        const uint32_t a = (I[1] >> 8) & 0xffu, b = (I[1] >> 16) & 0xffu, c = I[1] >> 24;
+        const uint32_t a = pf_ins_a(I[1]), b = pf_ins_b(I[1]), c = pf_ins_c(I[1]);
         if (tr & PF_TR_RA) live_w |= 1u << a;
         if (tr & PF_TR_RB) live_w |= 1u << b;
         if ((op >= PF_B_AND && op <= PF_B_ITE) || op == PF_B_SPILL || op == PF_ASSERT) live_b |= 1u << a;

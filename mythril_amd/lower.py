@@ -326,7 +326,7 @@ def _var_spill_uses() -> int:
 
 
 # ... and at least this many when a W_EXP runs before the variable's last use: the device
-# program's LDS spill slots (pathfeas.hip pass 4) are EXP's window-table entries, so such a
+# program's LDS spill slots (pf_devprog.h lds_spill_slots) are EXP's window-table entries, so such a
 # spill lands in scratch — config 3 regenerates instead (WRITE_SIZE 34 -> 13 MB per launch
 # at -0.3 %, profiles/r05z_spillexp_ab.md).  0 or <= PF_VAR_SPILL_USES: the one rule everywhere
 def _var_spill_uses_exp() -> int:

@@ -528,7 +528,7 @@ def test_spill_heavy_programs_match_oracle(engine, flags):
 
 
 def _forwarding_programs():
-    """Hand-built chains for the device program's forwarding pass (pathfeas.hip pass 5):
+    """Hand-built chains for the device program's forwarding pass (pf_devprog.h forward_results):
     a result read as both operands of the next instruction, a forwarded result also read
     later (its write-back kept), results feeding compares, ITE and B ops in between, a long
     mixed chain (DIV, EXP, shifts, CONCAT / EXTRACT), and the same chains at three W

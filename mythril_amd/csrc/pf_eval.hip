@@ -195,6 +195,12 @@ PF_INL u256 pow2m1(uint32_t k) {  // 2^k - 1
     return r;
 }
 
+// acc | (x & m) as one v_bitop3_b32 (truth table 0xF8, the first source the index's most
+// significant bit): one arm of gen_var's mask-and-or merge, m a 0 / ~0 lane mask
+PF_INL uint32_t or_masked(uint32_t acc, uint32_t x, uint32_t m) {
+    return __builtin_amdgcn_bitop3_b32(acc, x, m, (unsigned char)0xF8);
+}
+
 // boundary-arm deltas (gen_var): entry j in bits 3j..3j+2, biased by 2
 #define PF_BND_DELTA 0x2ca281b1aull
 
@@ -226,24 +232,53 @@ PF_INL uint4 philox_tail(uint4 c, uint32_t k0, uint32_t k1) {
 
 PF_INL uint4 philox(uint4 c, uint32_t k0, uint32_t k1) { return philox_tail<0>(c, k0, k1); }
 
-// philox(make_uint4(cand, v, z, 0), k0, k1), bit for bit, for the generator's counters:
-// only cand varies per lane, so round 1's second product (z * M1) is a constant, its first
-// (cand * M0, passed in as p0) is shared by the three blocks of a variable, and round 2's
-// first product has a wave-uniform operand and runs on the scalar unit — 17 per-lane
-// v_mad_u64_u32 per block instead of 20
-PF_INL uint4 philox_gen(uint64_t p0, uint32_t v, uint32_t z, uint32_t k0, uint32_t k1) {
-    const uint64_t p1 = (uint64_t)z * PF_PHILOX_M1;
-    const uint32_t x1 = (uint32_t)(p1 >> 32) ^ v ^ k0;  // uniform
-    const uint32_t y1 = (uint32_t)p1;                   // constant
-    const uint32_t z1 = (uint32_t)(p0 >> 32) ^ k1;      // per lane (counter word 3 is 0)
-    const uint32_t w1 = (uint32_t)p0;                   // per lane
+// The generator's Philox blocks of one variable, philox(make_uint4(cand, v, z, 0), k0, k1)
+// bit for bit: c[0] = the strategy block m (z = 2), c[1] = r0 (z = 0) and, with NB = 3,
+// c[2] = r1 (z = 1), as ONE straight-line sequence walked round by round.
+//  * Rounds 1-2 are specialised to the counter: only cand varies per lane, so round 1's
+//    second product (z * M1) is a constant, its first (cand * M0, passed in as p0) is shared
+//    by the blocks, and round 2's first product has a wave-uniform operand and runs on the
+//    scalar unit — 17 per-lane v_mad_u64_u32 per block instead of 20.
+//  * Rounds 3-10 issue the 2 * NB products of a round together, then its 2 * NB xors: a
+//    block alone is 8 dependent rounds of two multiplies each, and three blocks one after the
+//    other (one of them in a basic block of its own) were three such chains' latency.
+//  * The key schedule is wave-uniform and shared by the blocks: scalar adds, once.
+template <int NB>
+PF_INL void philox_gen3(uint64_t p0, uint32_t v, uint32_t k0, uint32_t k1, uint4 (&c)[NB]) {
+    static_assert(NB == 2 || NB == 3, "m and r0, or m, r0 and r1");
+    const uint32_t zs[3] = {2u, 0u, 1u};
+    const uint32_t z1 = (uint32_t)(p0 >> 32) ^ k1;  // per lane (counter word 3 is 0)
+    const uint32_t w1 = (uint32_t)p0;               // per lane
     k0 += PF_PHILOX_W0;
     k1 += PF_PHILOX_W1;
-    const uint64_t q0 = (uint64_t)x1 * PF_PHILOX_M0;    // uniform: scalar multiply
-    const uint64_t q1 = mul_wide(z1, PF_PHILOX_M1);
-    const uint4 c = make_uint4((uint32_t)(q1 >> 32) ^ (y1 ^ k0), (uint32_t)q1,
-                               ((uint32_t)(q0 >> 32) ^ k1) ^ w1, (uint32_t)q0);
-    return philox_tail<2>(c, k0 + PF_PHILOX_W0, k1 + PF_PHILOX_W1);
+    const uint64_t q1 = mul_wide(z1, PF_PHILOX_M1);  // the same product in every block
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const uint64_t p1 = (uint64_t)zs[b] * PF_PHILOX_M1;
+        const uint32_t x1 = (uint32_t)(p1 >> 32) ^ v ^ (k0 - PF_PHILOX_W0);  // uniform
+        const uint32_t y1 = (uint32_t)p1;                                   // constant
+        const uint64_t q0 = (uint64_t)x1 * PF_PHILOX_M0;  // uniform: scalar multiply
+        c[b] = make_uint4((uint32_t)(q1 >> 32) ^ (y1 ^ k0), (uint32_t)q1,
+                          ((uint32_t)(q0 >> 32) ^ k1) ^ w1, (uint32_t)q0);
+    }
+#pragma unroll
+    for (int i = 2; i < 10; i++) {
+        k0 += PF_PHILOX_W0;
+        k1 += PF_PHILOX_W1;
+        uint64_t a0[NB], a1[NB];
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            a0[b] = mul_wide(c[b].x, PF_PHILOX_M0);
+            a1[b] = mul_wide(c[b].z, PF_PHILOX_M1);
+        }
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const uint32_t hi0 = (uint32_t)(a0[b] >> 32), lo0 = (uint32_t)a0[b];
+            const uint32_t hi1 = (uint32_t)(a1[b] >> 32), lo1 = (uint32_t)a1[b];
+            c[b] = make_uint4(__builtin_amdgcn_bitop3_b32(hi1, c[b].y, k0, (unsigned char)0x96), lo1,
+                              __builtin_amdgcn_bitop3_b32(hi0, c[b].w, k1, (unsigned char)0x96), lo0);
+        }
+    }
 }
 
 struct SetCtx {
@@ -272,22 +307,37 @@ PF_INL uint32_t umod_rcp(uint32_t x, uint32_t d, uint32_t z) {
 }
 
 // candidate value of variable v (include/pf_bytecode.h generator contract).
-// Laid out for latency, not branches: the three Philox blocks depend only on (cand, v, key)
-// and are formed before anything waits on the schema, parent or constant loads; the
-// strategy arms (random / boundary / constant +-1 / parent mutation / small) are each
-// computed for every lane and selected, so the wave runs one straight sequence instead of
-// walking a lane-divergent if-chain; the per-variable kind stays a (uniform) branch.
+// Laid out for latency, not branches: the Philox blocks depend only on (cand, v, key) and
+// are formed interleaved (philox_gen3) before anything waits on the parent or constant
+// loads; the strategy arms (random / boundary / constant +-1 / parent mutation / small) are
+// each computed for every lane and merged by lane masks, so the wave runs one straight
+// sequence instead of walking a lane-divergent if-chain; the per-variable kind stays a
+// (uniform) branch.
 PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
     const uint4 sc = S.schema[v];  // uniform -> scalar load
     const uint64_t p0 = mul_wide(cand, PF_PHILOX_M0);  // round 1 of all three blocks
-    const uint4 m = philox_gen(p0, v, 2u, S.k0, S.k1);
     const uint32_t kind = sc.x & 0xffu, w = (sc.x >> 8) & 0x3ffu;
     const uint32_t hint0 = sc.y, hint1 = sc.z, pslot = sc.w;
+    // r1 only feeds limbs 4..7 of the random arm, which the final mask clears for w <= 128
+    // (bytes, selectors, small counters): the two-block form there, under a wave-uniform
+    // branch on the schema word
+    uint4 m, r0, r1 = make_uint4(0u, 0u, 0u, 0u);
+    if (w > 128u) {
+        uint4 c[3];
+        philox_gen3<3>(p0, v, S.k0, S.k1, c);
+        m = c[0]; r0 = c[1]; r1 = c[2];
+    } else {
+        uint4 c[2];
+        philox_gen3<2>(p0, v, S.k0, S.k1, c);
+        m = c[0]; r0 = c[1];
+    }
     // The one per-lane gather (a constant of the set for the +-1 arm, or the actor table
-    // entry) is issued here, in the entry block, so the two Philox blocks below cover its
-    // latency; inside the strategy branches it was waited for a dozen instructions after
-    // issue.  Its address is always in bounds: the pool carries one zero entry past its end
-    // (pathfeas.hip), so a set without constants reads that.
+    // entry) is issued here, right behind the blocks that give its address, and the parts of
+    // the arms that do not read it (the power of two, the boundary value, the small arm, the
+    // masks) stand between its issue and its first use; inside the strategy branches it was
+    // waited for a dozen instructions after issue.  Its address is always in bounds: the pool
+    // carries one zero entry past its end (pathfeas.hip), so a set without constants reads
+    // that.
     const uint32_t ai = m.y & 3u;
     const uint32_t act = (uint32_t)(kind == PF_VK_ACTOR) & (uint32_t)(ai < hint1);
     const uint32_t ci = S.n_const ? umod_rcp(m.y, S.n_const, S.nc_rcp) : 0u;
@@ -295,11 +345,6 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
     u256 g;
 #pragma unroll
     for (int i = 0; i < 8; i++) g.l[i] = gp[i];
-    const uint4 r0 = philox_gen(p0, v, 0u, S.k0, S.k1);
-    // r1 only feeds limbs 4..7 of the random arm, which the final mask clears for w <= 128
-    // (bytes, selectors, small counters): skipped there under a wave-uniform branch
-    uint4 r1 = make_uint4(0u, 0u, 0u, 0u);
-    if (w > 128u) r1 = philox_gen(p0, v, 1u, S.k0, S.k1);
     const bool has_parent = pslot != PF_NO_PARENT;
     u256 par = pf::zero256();
     if (has_parent) {
@@ -332,63 +377,67 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
         out.l[0] = r0.x & 1u;
     } else {
         const uint32_t sel = m.x & 15u;
-        // constant +-1 arm (sel 9..11)
-        u256 cst = rv;
-        if (S.n_const > 0u) {
-            const uint32_t dsel = m.z % 3u;  // +0, +1, -1
-            u256 dl;
-            dl.l[0] = dsel == 0u ? 0u : (dsel == 1u ? 1u : 0xffffffffu);
-#pragma unroll
-            for (int i = 1; i < 8; i++) dl.l[i] = dsel == 2u ? 0xffffffffu : 0u;
-            cst = pf::add256(g, dl);
-        }
+        // The strategy arms are mutually exclusive, so they are merged as mask-and-or: one
+        // 0 / ~0 lane mask per arm, formed once per variable (lane_mask keeps LLVM from
+        // turning the selects into divergent branches), and one v_bitop3_b32 per arm and limb
+        // instead of a chain of four selects and the actor select.  The lanes that no arm
+        // serves stay 0: half the lanes of a call value (PF_VK_VALUE).
+        const uint32_t zero = (uint32_t)(kind == PF_VK_VALUE) & (m.x >> 4) & 1u;
+        const uint32_t arm = (act | zero) ^ 1u;             // the lane takes a strategy arm
+        const uint32_t in_cst = (uint32_t)(sel - 9u <= 2u);  // constant +-1 arm (sel 9..11)
+        const uint32_t no_cst = (uint32_t)(S.n_const == 0u);  // uniform: that arm is random then
+        const uint32_t m_rv = pf::lane_mask(arm & ((uint32_t)(sel <= 4u) | (in_cst & no_cst)));
+        const uint32_t m_bnd = pf::lane_mask(arm & (uint32_t)(sel - 5u <= 3u));
+        // the actor set (transaction/symbolic.py:215), in most lanes of an actor, is the
+        // constant arm with delta 0: the gather reads the actor table entry there
+        const uint32_t m_cst = pf::lane_mask(act | (arm & in_cst & (no_cst ^ 1u)));
+        const uint32_t m_mut = pf::lane_mask(arm & (uint32_t)(sel - 12u <= 1u));
+        const uint32_t m_sm = pf::lane_mask(arm & (uint32_t)(sel >= 14u));
         // boundary arm (sel 5..8): {0, 1, 2, 3, 2^w-1, 2^w-2, 2^(w-1), 2^(w-1)-1, 2^k, 2^k-1,
         // 2^k+1, 2^160-1}[j] mod 2^w as one formula, (j >= 6 ? 2^p : 0) + delta
         // one power of two serves both the boundary arm (2^p) and the parent-mutation arm
         // (2^k, k = m[2] % w): a lane takes one arm, so the exponent is selected per lane
-        // (w is uniform; a power of two — every 256-bit variable — needs no division)
+        // (w is uniform; a power of two — every 256-bit variable — needs no division).
+        // Exponent 256 is no limb's: the power is 0 there (j <= 5)
         const uint32_t j = m.y % 12u, k = (w & (w - 1u)) == 0u ? (m.z & (w - 1u)) : m.z % w;
-        const uint32_t p = j <= 7u ? w - 1u : (j <= 10u ? k : 160u);
+        const uint32_t p = j <= 5u ? 256u : (j <= 7u ? w - 1u : (j <= 10u ? k : 160u));
         const u256 pw = pow2(sel <= 8u ? p : k);
         u256 bnd;
         {
             // delta by j, 3 bits per entry biased by 2 (a ternary chain here became a
             // divergent if-chain): j 0..11 -> 0 1 2 3 -1 -2 0 -1 0 -1 1 -1
             const int32_t delta = (int32_t)((PF_BND_DELTA >> (3u * j)) & 7ull) - 2;
-            u256 base = pw;
-            const uint32_t usepow = j >= 6u ? 0xffffffffu : 0u;
             u256 dl;
             dl.l[0] = (uint32_t)delta;
 #pragma unroll
             for (int i = 1; i < 8; i++) dl.l[i] = delta < 0 ? 0xffffffffu : 0u;
-#pragma unroll
-            for (int i = 0; i < 8; i++) base.l[i] &= usepow;
-            bnd = pf::add256(base, dl);
+            bnd = pf::add256(pw, dl);
         }
+        // limb 0 only: the small arm (sel 14..15), 1..16 random low bits, and, without a
+        // parent, the mutation arm's random byte (sel 12..13)
+        const uint32_t nb = 1u + (m.y & 15u);
+        const uint32_t lo_bits = (((1u << nb) - 1u) & m_sm) | (has_parent ? 0u : (0xffu & m_mut));
+        // constant +-1 arm: the first use of the gather
+        u256 cst;
+        {
+            const uint32_t dsel = m.z % 3u;  // +0, +1, -1
+            const uint32_t neg = 0u - ((uint32_t)(dsel == 2u) & (act ^ 1u));
+            u256 dl;
+            dl.l[0] = neg | ((uint32_t)(dsel == 1u) & (act ^ 1u));
+#pragma unroll
+            for (int i = 1; i < 8; i++) dl.l[i] = neg;
+            cst = pf::add256(g, dl);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            out.l[i] = or_masked(or_masked(rv.l[i] & m_rv, bnd.l[i], m_bnd), cst.l[i], m_cst);
+        out.l[0] |= r0.x & lo_bits;
         // parent-mutation arm (sel 12..13): one bit of the parent flipped in a quarter of
-        // the lanes; without a parent, a random byte
-        u256 mut = pf::zero256();
+        // the lanes
         if (has_parent) {
             const uint32_t flip = (m.y & 3u) == 0u ? 0xffffffffu : 0u;
 #pragma unroll
-            for (int i = 0; i < 8; i++) mut.l[i] = par.l[i] ^ (pw.l[i] & flip);
-        } else {
-            mut.l[0] = r0.x & 0xffu;
-        }
-        // small arm (sel 14..15): 1..16 random low bits
-        const uint32_t nb = 1u + (m.y & 15u);
-        const uint32_t small = r0.x & ((nb >= 32u) ? 0xffffffffu : ((1u << nb) - 1u));
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const uint32_t sm = i == 0 ? small : 0u;
-            out.l[i] = sel <= 4u ? rv.l[i]
-                     : (sel <= 8u ? bnd.l[i] : (sel <= 11u ? cst.l[i] : (sel <= 13u ? mut.l[i] : sm)));
-            // the actor set (transaction/symbolic.py:215) in most lanes
-            out.l[i] = act ? g.l[i] : out.l[i];
-        }
-        if (kind == PF_VK_VALUE) {  // uniform: call values are 0 in half the lanes
-#pragma unroll
-            for (int i = 0; i < 8; i++) out.l[i] = (m.x & 16u) ? 0u : out.l[i];
+            for (int i = 0; i < 8; i++) out.l[i] = or_masked(out.l[i], par.l[i] ^ (pw.l[i] & flip), m_mut);
         }
         if (kind == PF_VK_CDBYTE) {
             // calldata bytes (uniform branch, after the generic arms so nothing of it lives

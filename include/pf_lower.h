@@ -137,7 +137,7 @@ void* pflt_store_new(void);
 #define PFLT_FEAT_EXPLICIT 1u
 #define PFLT_FEAT_SYNTH 2u
 uint32_t pflt_features(void);
-/* BASELINE config 3's synthetic DAGs natively: results[i] = the lowered program of
+/* BASELINE config 3's synthetic DAGs natively (csrc/pf_synth.cpp): results[i] = the lowered program of
  * mythril_amd.synth.random_dag_set(first_id + i, plant) bit for bit (numpy's Philox4x64
  * Generator stream restated), for pflt_pack_batch; cdf = the op mix's 8 normalised cumulative
  * probabilities; witness_limbs (optional, 8 x 8 u32 per DAG) and n_vars_out (optional) get

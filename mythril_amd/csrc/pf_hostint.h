@@ -2,10 +2,13 @@
  * pf_hostint.h — the host's 256-bit integers and its one evaluator of bytecode opcodes on
  * them: what op(a, b) is at width w under the total-division conventions of
  * include/pf_bytecode.h.  The fold pass of device programs (pf_fold.h), the hint solver
- * (pf_seed.cpp) and Power's concrete facts (pf_terms.cpp) all ask it; so a new opcode or
- * convention is written here once.  Also the keyed hash behind PF_W_HASH (two Philox4x32-10
- * blocks) and zlib's CRC-32, which salts it with a function's name.  tests/test_host_ops.py
- * pins every opcode against the golden vectors and the Python oracle.
+ * (pf_seed.cpp), Power's concrete facts (pf_terms.cpp) and the planted values of the config-3
+ * generator (pf_synth.cpp) all ask it; so a new opcode or convention is written here once,
+ * and so are the algorithms that make it fast: Knuth's algorithm D on 64-bit digits, the low
+ * half of a product alone, powers that stop at the exponent's top bit.  Also the keyed hash
+ * behind PF_W_HASH (two Philox4x32-10 blocks) and zlib's CRC-32, which salts it with a
+ * function's name.  tests/test_host_ops.py pins every opcode against the golden vectors and
+ * the Python oracle.
  * Host C++ only, header-only, no HIP.  Values are 4 x u64 limbs, little-endian; constant
  * pools keep 8 x u32 (from32 / to32).
  */
@@ -146,10 +149,17 @@ inline void mul_full(const U& a, const U& b, U* lo, U* hi) {
         hi->w[i] = r[i + 4];
     }
 }
-inline U mul(const U& a, const U& b) {
-    U lo, hi;
-    mul_full(a, b, &lo, &hi);
-    return lo;
+inline U mul(const U& a, const U& b) {  // the low 256 bits alone: 10 limb products
+    U r;
+    for (int i = 0; i < 4; i++) {
+        unsigned __int128 c = 0;
+        for (int j = 0; i + j < 4; j++) {
+            c += (unsigned __int128)a.w[i] * b.w[j] + r.w[i + j];
+            r.w[i + j] = (uint64_t)c;
+            c >>= 64;
+        }
+    }
+    return r;
 }
 inline void divmod(const U& a, const U& b, U* q, U* r) {  // b != 0
     if (lt(a, b)) {
@@ -170,27 +180,67 @@ inline void divmod(const U& a, const U& b, U* q, U* r) {  // b != 0
         *r = U::of((uint64_t)rem);
         return;
     }
-    // restoring division from the first quotient bit that can be set (the bits of a above
-    // it are below b)
-    const int k0 = (int)bitlen(a) - (int)bitlen(b);
-    U Q, R = shr(a, (unsigned)k0 + 1u);
-    for (int k = k0; k >= 0; k--) {
-        R = shl(R, 1);
-        if (bit(a, (unsigned)k)) R.w[0] |= 1;
-        if (!lt(R, b)) {
-            R = sub(R, b);
-            Q.w[k / 64] |= 1ull << (k % 64);
+    // Knuth's algorithm D on 64-bit digits (Hacker's Delight divmnu): n >= 2 digits of b
+    // under m >= n of a, both shifted so that b's top digit has its top bit set
+    typedef unsigned __int128 u128;
+    int n = 4, m = 4;
+    while (!b.w[n - 1]) n--;
+    while (!a.w[m - 1]) m--;
+    const int s = __builtin_clzll(b.w[n - 1]);
+    uint64_t vn[4], un[5];
+    for (int i = n - 1; i > 0; i--) vn[i] = (b.w[i] << s) | (s ? b.w[i - 1] >> (64 - s) : 0);
+    vn[0] = b.w[0] << s;
+    un[m] = s ? a.w[m - 1] >> (64 - s) : 0;
+    for (int i = m - 1; i > 0; i--) un[i] = (a.w[i] << s) | (s ? a.w[i - 1] >> (64 - s) : 0);
+    un[0] = a.w[0] << s;
+    U Q, R;
+    for (int j = m - n; j >= 0; j--) {
+        // the digit's estimate from the top two digits over b's top one, at most 2 too large
+        // once the third digit is looked at; a top digit equal to b's makes it 2^64 - 1
+        uint64_t qhat = ~0ull;
+        u128 rhat = (u128)un[j + n - 1] + vn[n - 1];
+        if (un[j + n] < vn[n - 1]) {
+            const u128 num = ((u128)un[j + n] << 64) | un[j + n - 1];
+            qhat = (uint64_t)(num / vn[n - 1]);
+            rhat = num - (u128)qhat * vn[n - 1];
         }
+        while (!(rhat >> 64) && (u128)qhat * vn[n - 2] > ((rhat << 64) | un[j + n - 2])) {
+            qhat--;
+            rhat += vn[n - 1];
+        }
+        uint64_t k = 0;  // un[j .. j + n] -= qhat * vn
+        for (int i = 0; i < n; i++) {
+            const u128 p = (u128)qhat * vn[i] + k;
+            const uint64_t x = un[i + j], lo = (uint64_t)p;
+            un[i + j] = x - lo;
+            k = (uint64_t)(p >> 64) + (x < lo);
+        }
+        const bool over = un[j + n] < k;
+        un[j + n] -= k;
+        if (over) {  // one too large still: add b back
+            qhat--;
+            u128 c = 0;
+            for (int i = 0; i < n; i++) {
+                c += (u128)un[i + j] + vn[i];
+                un[i + j] = (uint64_t)c;
+                c >>= 64;
+            }
+            un[j + n] += (uint64_t)c;
+        }
+        Q.w[j] = qhat;
     }
+    for (int i = 0; i < n - 1; i++) R.w[i] = (un[i] >> s) | (s ? un[i + 1] << (64 - s) : 0);
+    R.w[n - 1] = un[n - 1] >> s;
     *q = Q;
     *r = R;
 }
 inline U powmod(U a, const U& e, unsigned w) {  // a^e mod 2^w
-    U r = U::of(1);
     const unsigned n = bitlen(e);
+    if (!(a.w[0] & 1u) && n > 8) return U();  // even base, e >= 256: 2^256 divides the power
+    U r = U::of(1);
     for (unsigned k = 0; k < n; k++) {
         if (bit(e, k)) r = mul(r, a);
-        a = mul(a, a);
+        if (k + 1 < n) a = mul(a, a);
     }
     return mw(r, w);
 }

@@ -8,7 +8,8 @@
 // and then the hint derivation (pfl_hints) and register allocation (pfl_lower) of the same
 // library, so a bucket goes from terms to a program without a Python DAG in between.
 // tests/test_native_terms.py checks the node tables, variables, witness metadata and
-// programs against the Python lowering.  Host code, no HIP.
+// programs against the Python lowering.  The Dag, the Result and emit_program are pf_dag.h's,
+// shared with the config-3 generator (pf_synth.cpp).  Host code, no HIP.
 //
 // Terms live in a store the host fills once per term (hash-consed Python terms are immortal,
 // so a term's store id never changes): children before parents.  A lowering call names the
@@ -18,7 +19,6 @@
 #include <cctype>
 #include <cstdlib>
 #include <tuple>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -33,101 +33,17 @@
 
 #include "../../include/pf_bytecode.h"
 #include "../../include/pf_lower.h"
+#include "pf_dag.h"
 #include "pf_hostint.h"
 #include "pf_pool.h"
 
+using namespace pf_dag;  // the DAG, Result, emit_program; Big and C8; TermError, t_err, lerr
+
 namespace {
-
-thread_local std::string t_err;
-
-struct TermError {
-    int rc;
-};
 
 #ifndef PF_MAX_TERM_DEPTH
 #define PF_MAX_TERM_DEPTH 5000u
 #endif
-
-[[noreturn]] void lerr(const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    t_err = buf;
-    throw TermError{-2};
-}
-
-// ---- big unsigned integers (term constants: any width) ---------------------------------
-typedef std::vector<uint32_t> Big;  // little-endian limbs, no trailing-zero normalisation
-
-uint32_t limb(const Big& v, size_t i) { return i < v.size() ? v[i] : 0u; }
-
-Big mask_big(const Big& v, uint32_t w) {
-    const size_t nl = (w + 31) / 32;
-    Big r(nl, 0u);
-    for (size_t i = 0; i < nl; i++) r[i] = limb(v, i);
-    if (w % 32 && nl) r[nl - 1] &= (1u << (w % 32)) - 1u;
-    return r;
-}
-
-Big shr_big(const Big& v, uint32_t s) {
-    const size_t q = s / 32, b = s % 32;
-    Big r;
-    for (size_t i = q; i < v.size(); i++) {
-        uint32_t x = v[i] >> b;
-        if (b && i + 1 < v.size()) x |= v[i + 1] << (32 - b);
-        r.push_back(x);
-    }
-    return r;
-}
-
-bool big_eq(const Big& a, const Big& b) {
-    const size_t n = std::max(a.size(), b.size());
-    for (size_t i = 0; i < n; i++)
-        if (limb(a, i) != limb(b, i)) return false;
-    return true;
-}
-
-bool big_zero(const Big& a) {
-    for (uint32_t x : a)
-        if (x) return false;
-    return true;
-}
-
-uint32_t bitlen(const Big& a) {
-    for (size_t i = a.size(); i-- > 0;)
-        if (a[i]) return (uint32_t)(32 * i + 32 - __builtin_clz(a[i]));
-    return 0;
-}
-
-// ---- 256-bit constants (DAG constant nodes) ------------------------------------------------
-struct C8 {
-    uint32_t l[8];
-    bool operator==(const C8& o) const { return memcmp(l, o.l, sizeof(l)) == 0; }
-};
-
-C8 c8_of(const Big& v, uint32_t w) {  // v masked to w <= 256 bits
-    C8 c;
-    const Big m = mask_big(v, w);
-    for (int i = 0; i < 8; i++) c.l[i] = limb(m, i);
-    return c;
-}
-
-C8 c8_small(uint64_t x, uint32_t w) {
-    Big b = {(uint32_t)x, (uint32_t)(x >> 32)};
-    return c8_of(b, w);
-}
-
-Big big_of(const C8& c) { return Big(c.l, c.l + 8); }
-
-// to and from the integers that compute (pf_hostint.h)
-pf_host::U u_of(const C8& c) { return pf_host::U::from32(c.l); }
-C8 c8_of(const pf_host::U& u) {
-    C8 c;
-    u.to32(c.l);
-    return c;
-}
 
 // ---- the term store -------------------------------------------------------------------
 struct TermRec {
@@ -216,295 +132,19 @@ struct Store {
     std::vector<int32_t> kfam, uf, ugrp;
 };
 
-// ---- the DAG (mythril_amd/lower.py Dag) ---------------------------------------------------
-constexpr uint32_t K_VAR = PFL_K_VAR, K_CONST = PFL_K_CONST, K_BCONST = PFL_K_BCONST,
-                   K_BVAR = PFL_K_BVAR;
-
-struct DNode {
-    uint32_t kind, width, nargs;
-    int32_t args[3];
-    uint32_t aux;
-    C8 cv;  // K_CONST value
-    bool is_bool;
-};
-
-struct DVar {
-    std::string name;
-    uint32_t width, kind, hint0, hint1;
-    bool has_parent;
-    C8 parent;
-};
-
-struct NodeKey {  // the hash-consing key of a node (lower.py Node tuple)
-    uint32_t kind, width, nargs, aux;
-    int32_t args[3];
-    uint32_t is_bool;
-    C8 cv;
-    bool operator==(const NodeKey& o) const { return memcmp(this, &o, sizeof(NodeKey)) == 0; }
-};
-
-struct NodeKeyHash {
-    size_t operator()(const NodeKey& k) const {
-        const uint32_t* w = (const uint32_t*)&k;
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (size_t i = 0; i < sizeof(NodeKey) / 4; i++) h = (h ^ w[i]) * 0x100000001B3ull;
-        return (size_t)(h ^ (h >> 29));
-    }
-};
-
-// Hash-consing table of a DAG: open addressing over node ids (the key is the node itself),
-// linear probing, grown at half load.  A std::unordered_map<NodeKey, id> allocated one
-// 80-byte node per DAG node and, reserved for 4,096 entries per job, zeroed a 32 KB bucket
-// array for buckets of a few dozen nodes — allocation churn that was a large share of a
-// single query's lowering.
-struct NodeTable {
-    std::vector<int32_t> slot;   // -1 = empty
-    size_t used = 0;
-    void clear() { std::vector<int32_t>().swap(slot); used = 0; }
-};
-
-inline uint64_t node_hash(uint32_t kind, uint32_t width, uint32_t nargs, const int32_t* args, uint32_t aux,
-                          bool is_bool, const C8* cv) {
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    auto mix = [&](uint32_t w) { h = (h ^ w) * 0x100000001B3ull; };
-    mix(kind);
-    mix(width);
-    mix(nargs);
-    mix(aux);
-    for (uint32_t i = 0; i < nargs; i++) mix((uint32_t)args[i]);
-    mix(is_bool ? 1u : 0u);
-    if (kind == K_CONST)  // a constant without a value given is the zero constant
-        for (int i = 0; i < 8; i++) mix(cv ? cv->l[i] : 0u);
-    // fmix64: the table indexes with the low bits, which the FNV products alone spread poorly
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    return h ^ (h >> 33);
+// ^keccak256_(\d+)(-1)?$: the digits as written (the independence keys tell "007" from "7";
+// the lowering takes their number) and whether it is the inverse
+bool keccak_app(const std::string& f, std::string* n, bool* inv) {
+    static const char pre[] = "keccak256_";
+    if (f.compare(0, sizeof(pre) - 1, pre) != 0) return false;
+    size_t i = sizeof(pre) - 1, j = i;
+    while (j < f.size() && isdigit((unsigned char)f[j])) j++;
+    if (j == i) return false;
+    *n = f.substr(i, j - i);
+    if (j == f.size()) { *inv = false; return true; }
+    if (f.compare(j, std::string::npos, "-1") == 0) { *inv = true; return true; }
+    return false;
 }
-
-struct Dag {
-    std::vector<DNode> nodes;
-    std::vector<int32_t> roots;
-    std::vector<DVar> vars;
-    std::vector<C8> forced;
-    NodeTable memo;
-    std::unordered_map<std::string, int32_t> var_index;
-
-    explicit Dag(size_t reserve = 64) {
-        size_t cap = 16;
-        while (cap < 2 * reserve) cap <<= 1;
-        memo.slot.assign(cap, -1);
-        nodes.reserve(reserve);
-    }
-
-    bool same(const DNode& n, uint32_t kind, uint32_t width, const int32_t* args, uint32_t nargs, uint32_t aux,
-              bool is_bool, const C8* cv) const {
-        if (n.kind != kind || n.width != width || n.nargs != nargs || n.aux != aux || n.is_bool != is_bool) return false;
-        for (uint32_t i = 0; i < nargs; i++)
-            if (n.args[i] != args[i]) return false;
-        if (kind == K_CONST) {
-            static const C8 zero{};
-            return memcmp(n.cv.l, (cv ? cv : &zero)->l, sizeof(n.cv.l)) == 0;
-        }
-        return true;
-    }
-
-    void grow() {
-        std::vector<int32_t> old;
-        old.swap(memo.slot);
-        memo.slot.assign(old.size() * 2, -1);
-        const size_t mask = memo.slot.size() - 1;
-        for (int32_t id : old) {
-            if (id < 0) continue;
-            const DNode& n = nodes[(size_t)id];
-            size_t h = (size_t)node_hash(n.kind, n.width, n.nargs, n.args, n.aux, n.is_bool, &n.cv) & mask;
-            while (memo.slot[h] >= 0) h = (h + 1) & mask;
-            memo.slot[h] = id;
-        }
-    }
-
-    int32_t add_n(uint32_t kind, uint32_t width, const int32_t* args, uint32_t nargs, uint32_t aux,
-                  bool is_bool, const C8* cv = nullptr) {
-        if (memo.slot.empty()) memo.slot.assign(16, -1);
-        const size_t mask = memo.slot.size() - 1;
-        size_t h = (size_t)node_hash(kind, width, nargs, args, aux, is_bool, cv) & mask;
-        for (;;) {
-            const int32_t id = memo.slot[h];
-            if (id < 0) break;
-            if (same(nodes[(size_t)id], kind, width, args, nargs, aux, is_bool, cv)) return id;
-            h = (h + 1) & mask;
-        }
-        DNode n;
-        memset(&n, 0, sizeof(n));
-        n.kind = kind;
-        n.width = width;
-        n.nargs = nargs;
-        for (uint32_t i = 0; i < nargs; i++) n.args[i] = args[i];
-        n.aux = aux;
-        if (cv) n.cv = *cv;
-        n.is_bool = is_bool;
-        const int32_t id = (int32_t)nodes.size();
-        nodes.push_back(n);
-        memo.slot[h] = id;
-        if (2 * ++memo.used > memo.slot.size()) grow();
-        return id;
-    }
-
-    int32_t add(uint32_t kind, uint32_t width, std::initializer_list<int32_t> args, uint32_t aux,
-                bool is_bool, const C8* cv = nullptr) {
-        return add_n(kind, width, args.begin(), (uint32_t)args.size(), aux, is_bool, cv);
-    }
-
-    uint32_t force_consts(const std::vector<C8>& vals) {
-        const uint32_t start = (uint32_t)forced.size();
-        forced.insert(forced.end(), vals.begin(), vals.end());
-        return start;
-    }
-
-    int32_t var(const std::string& name, uint32_t width, uint32_t kind, uint32_t h0, uint32_t h1,
-                bool has_parent, const C8& parent, bool* created) {
-        auto it = var_index.find(name);
-        uint32_t idx;
-        *created = false;
-        if (it == var_index.end()) {
-            idx = (uint32_t)vars.size();
-            DVar v{name, width, kind, h0, h1, has_parent, parent};
-            vars.push_back(v);
-            var_index.emplace(name, (int32_t)idx);
-            *created = true;
-        } else {
-            idx = (uint32_t)it->second;
-        }
-        if (kind == PF_VK_BOOL) return add(K_BVAR, 1, {}, idx, true);
-        return add(K_VAR, width, {}, idx, false);
-    }
-
-    int32_t cnst(const C8& v, uint32_t width) {
-        if (width == 256) return add(K_CONST, width, {}, 0, false, &v);
-        C8 m = c8_of(big_of(v), width);
-        return add(K_CONST, width, {}, 0, false, &m);
-    }
-    int32_t cnst(uint64_t v, uint32_t width) { return cnst(c8_small(v, width), width); }
-    int32_t bconst(bool v) { return add(K_BCONST, 1, {}, v ? 1u : 0u, true); }
-
-    const C8* cval(int32_t i) const { return nodes[i].kind == K_CONST ? &nodes[i].cv : nullptr; }
-
-    int32_t op(uint32_t opc, uint32_t w, std::initializer_list<int32_t> args, uint32_t aux = 0) {
-        const int32_t r = simplify(opc, w, args.begin(), aux);
-        if (r >= 0) return r;
-        return add_n(opc, w, args.begin(), (uint32_t)args.size(), aux, opc >= PF_B_CONST);
-    }
-
-    // Dag._simplify: the word-slicing rewrites (lower.py)
-    int32_t simplify(uint32_t opc, uint32_t w, const int32_t* args, uint32_t aux) {
-        if (opc == PF_W_UDIV) {
-            const C8* c = cval(args[1]);
-            if (c) {
-                const Big cb = big_of(*c);
-                const uint32_t bl = bitlen(cb);
-                if (bl && bitlen(mask_big(shr_big(cb, 0), bl - 1)) == 0) {  // power of two
-                    const uint32_t k = bl - 1;
-                    return k == 0 ? args[0] : op(PF_W_LSHR, w, {args[0], cnst(k, w)});
-                }
-            }
-        } else if (opc == PF_W_LSHR) {
-            const C8* c = cval(args[1]);
-            const DNode x = nodes[args[0]];
-            if (c && bitlen(big_of(*c)) <= 32 && c->l[0] < w) {
-                const uint32_t k = c->l[0];
-                if (k == 0) return args[0];
-                if (x.kind == PF_W_MOV) {
-                    const int32_t inner = x.args[0];
-                    const uint32_t wi = nodes[inner].width;
-                    if (k >= wi) return cnst(0, w);
-                    return op(PF_W_MOV, w, {op(PF_W_EXTRACT, wi - k, {inner}, k)});
-                }
-                if (x.kind == PF_W_CONCAT) return op(PF_W_MOV, w, {op(PF_W_EXTRACT, w - k, {args[0]}, k)});
-            }
-        } else if (opc == PF_W_AND) {
-            for (int xi = 0; xi < 2; xi++) {
-                const int ci = 1 - xi;
-                const C8* c = cval(args[ci]);
-                if (!c) continue;
-                const Big cb = big_of(*c);
-                const uint32_t bl = bitlen(cb);
-                if (bl == 0) continue;
-                // c == 2^bl - 1
-                bool ones = true;
-                for (uint32_t i = 0; i < bl; i++)
-                    if (!((cb[i / 32] >> (i % 32)) & 1u)) { ones = false; break; }
-                if (ones && bl < w) return op(PF_W_MOV, w, {op(PF_W_EXTRACT, bl, {args[xi]}, 0)});
-            }
-        } else if (opc == PF_W_EXTRACT) {
-            const DNode x = nodes[args[0]];
-            if (aux == 0 && w == x.width) return args[0];
-            if (x.kind == PF_W_CONCAT) {
-                const int32_t hi = x.args[0], lo = x.args[1];
-                const uint32_t wl = x.aux;
-                if (aux >= wl) return op(PF_W_EXTRACT, w, {hi}, aux - wl);
-                if (aux + w <= wl) return op(PF_W_EXTRACT, w, {lo}, aux);
-                const int32_t top = op(PF_W_EXTRACT, aux + w - wl, {hi}, 0);
-                const int32_t bot = op(PF_W_EXTRACT, wl - aux, {lo}, aux);
-                return op(PF_W_CONCAT, w, {top, bot}, wl - aux);
-            }
-            if (x.kind == PF_W_MOV) {
-                const int32_t inner = x.args[0];
-                const uint32_t wi = nodes[inner].width;
-                if (aux + w <= wi) return op(PF_W_EXTRACT, w, {inner}, aux);
-                if (aux >= wi) return cnst(0, w);
-            }
-            if (x.kind == K_CONST) return cnst(c8_of(shr_big(big_of(x.cv), aux), w), w);
-        } else if (opc == PF_W_MOV) {
-            const DNode x = nodes[args[0]];
-            if (x.width == w) return args[0];
-            if (x.kind == PF_W_MOV) return op(PF_W_MOV, w, {x.args[0]});
-            if (x.kind == K_CONST) return cnst(x.cv, w);
-        } else if (opc == PF_B_EQ) {
-            for (int xi = 0; xi < 2; xi++) {
-                const int ci = 1 - xi;
-                const C8* c = cval(args[ci]);
-                const DNode x = nodes[args[xi]];
-                if (c && x.kind == PF_W_MOV) {
-                    const uint32_t wy = nodes[x.args[0]].width;
-                    if (!big_zero(shr_big(big_of(*c), wy))) return bconst(false);
-                    return op(PF_B_EQ, wy, {x.args[0], cnst(*c, wy)});
-                }
-            }
-        }
-        return -1;
-    }
-
-    // the calldata-byte arm's word constants (Dag.word_constants / finalize_word_hints)
-    void finalize_word_hints() {
-        bool any = false;
-        for (const DVar& v : vars) any |= v.kind == PF_VK_CDBYTE;
-        if (!any) return;
-        std::vector<C8> words;
-        for (const DNode& nd : nodes) {
-            if (!(nd.kind == PF_B_EQ || nd.kind == PF_B_ULT || nd.kind == PF_B_ULE ||
-                  nd.kind == PF_B_SLT || nd.kind == PF_B_SLE))
-                continue;
-            const DNode& a = nodes[nd.args[0]];
-            const DNode& b = nodes[nd.args[1]];
-            const DNode* pairs[2][2] = {{&a, &b}, {&b, &a}};
-            for (auto& pr : pairs) {
-                const DNode* c = pr[0];
-                const DNode* other = pr[1];
-                if (c->kind != K_CONST) continue;
-                if (other->kind == K_VAR && vars[other->aux].kind == PF_VK_SMALL) continue;
-                bool seen = false;
-                for (const C8& x : words) seen |= x == c->cv;
-                if (!seen) words.push_back(c->cv);
-            }
-        }
-        if (words.size() > 0xFFF) words.resize(0xFFF);
-        if (words.empty() || forced.size() >= 0xFFF) return;
-        const uint32_t start = force_consts(words);
-        for (DVar& v : vars)
-            if (v.kind == PF_VK_CDBYTE) v.hint0 = (v.hint0 & 0xFFu) | ((uint32_t)words.size() << 8) | (start << 20);
-    }
-};
 
 // ---- term lowering (to_dag.TermLowering) ---------------------------------------------------
 enum TOp : uint32_t {
@@ -561,13 +201,6 @@ struct KSpec {
     bool has_lo;
     C8 base;
     std::vector<std::pair<Big, C8>> concrete;  // insertion order (dict order)
-};
-
-// var_terms descriptors handed back to the host (Lowered.var_terms)
-struct VarTerm {
-    uint32_t type;  // PFLT_VT_TERM / PFLT_VT_SELECT / PFLT_VT_EXTRACT
-    uint32_t a, b;  // term id | (array id, index id) | (term id, lo)
-    uint32_t c;     // extract hi
 };
 
 // term id -> Val memo of a lowering: open addressing over the term ids, values in a deque (a
@@ -1317,21 +950,10 @@ struct Lowering {
     }
 
     static bool keccak_name(const std::string& f, uint32_t* n, bool* inv) {
-        static const char pre[] = "keccak256_";
-        if (f.compare(0, sizeof(pre) - 1, pre) != 0) return false;
-        size_t i = sizeof(pre) - 1, j = i;
-        while (j < f.size() && isdigit((unsigned char)f[j])) j++;
-        if (j == i) return false;
-        *n = (uint32_t)strtoul(f.c_str() + i, nullptr, 10);
-        if (j == f.size()) {
-            *inv = false;
-            return true;
-        }
-        if (f.compare(j, std::string::npos, "-1") == 0) {
-            *inv = true;
-            return true;
-        }
-        return false;
+        std::string digits;
+        if (!keccak_app(f, &digits, inv)) return false;
+        *n = (uint32_t)strtoul(digits.c_str(), nullptr, 10);
+        return true;
     }
 
     // ---- explicit-model leaves (ExplicitLowering._leaf / _select / _apply) ----------------
@@ -1545,43 +1167,6 @@ struct Lowering {
     }
 };
 
-// ---- results ------------------------------------------------------------------------------
-struct Result {
-    Dag dag;
-    std::vector<VarTerm> var_terms;
-    std::vector<uint32_t> uf_apps;
-    std::vector<uint32_t> reads;   // (array id, index id) pairs, arrays in insertion order
-    std::vector<uint32_t> read_counts;  // entries per array, same order
-    std::vector<uint32_t> code;    // n_ins x 4
-    std::vector<uint32_t> consts;  // n_const x 8
-    std::vector<uint32_t> packed_nodes, pool;  // pack_nodes of the DAG (tests)
-    std::string names;             // variable names, '\0'-separated
-    uint32_t n_wregs = 0;
-    int n_sat = 0;
-    int rc = 0;                    // 0, or the failure code (-2 LoweringError -> z3, -1 / -3 ...)
-    std::string err;               // the failure message
-    std::vector<uint32_t> in_roots;  // the bucket's conjuncts (the re-check's roots)
-    bool parented = false;         // a parent model seeded some variable
-};
-
-void pack(const Dag& d, std::vector<uint32_t>* nodes, std::vector<uint32_t>* pool) {
-    nodes->clear();
-    pool->clear();
-    uint32_t np = 0;
-    for (const DNode& n : d.nodes) {
-        uint32_t aux = n.aux;
-        if (n.kind == K_CONST) {
-            aux = np++;
-            pool->insert(pool->end(), n.cv.l, n.cv.l + 8);
-        }
-        const uint32_t a0 = n.nargs > 0 ? (uint32_t)n.args[0] : 0u, a1 = n.nargs > 1 ? (uint32_t)n.args[1] : 0u,
-                       a2 = n.nargs > 2 ? (uint32_t)n.args[2] : 0u;
-        const uint32_t rec[8] = {n.kind, n.width, n.nargs, a0, a1, a2, aux, n.is_bool ? 1u : 0u};
-        nodes->insert(nodes->end(), rec, rec + 8);
-    }
-    if (nodes->empty()) nodes->assign(8, 0u);
-}
-
 // parent values: per name its limb count then the limbs (any width); reads (array id,
 // index id) with 8 limbs each
 void fill_parents(Parents* P, const char* par_names, const uint32_t* par_name_vals, size_t n_par_names,
@@ -1598,79 +1183,6 @@ void fill_parents(Parents* P, const char* par_names, const uint32_t* par_name_va
         C8 c;
         memcpy(c.l, par_read_vals + 8 * i, 32);
         P->set_read(std::make_pair(par_reads[2 * i], par_reads[2 * i + 1]), c);
-    }
-}
-
-// Register allocation + emission of a finished DAG into R (lower.lower(dag): narrow register
-// file first, wide when the narrow program is spill-heavy and the wide one at least halves
-// its spill code).  Throws TermError like the lowering.
-void emit_program(Dag& d, Result* R) {
-    d.finalize_word_hints();
-    pack(d, &R->packed_nodes, &R->pool);
-    std::vector<uint32_t> forced;
-    for (const C8& c : d.forced) forced.insert(forced.end(), c.l, c.l + 8);
-    std::vector<uint32_t> roots2(d.roots.begin(), d.roots.end());
-    if (roots2.empty()) roots2.push_back(0);
-    const uint32_t tries[2] = {PF_NW_NARROW, PF_NW};
-    int rc = -2;
-    // the narrow program unless its spill code exceeds an eighth of it and the wide
-    // register file at least halves that (lower.py lower(): the same policy)
-    bool have_narrow = false;
-    std::vector<uint32_t> n_code, n_consts;
-    size_t n_spill_narrow = 0;
-    // output scratch per thread, grown but never cleared (pfl_lower writes what it
-    // reports); the result keeps only the words written
-    thread_local std::vector<uint32_t> code_buf, const_buf;
-    for (int ti = 0; ti < 2; ti++) {
-        size_t cap_i = 16 * d.nodes.size() + 64 + 4 * d.roots.size();
-        size_t cap_c = R->pool.size() / 8 + d.forced.size() + 1;
-        size_t ni = 0, nc = 0;
-        for (int attempt = 0; attempt < 4; attempt++) {
-            if (code_buf.size() < 4 * cap_i) code_buf.resize(4 * cap_i);
-            if (const_buf.size() < 8 * cap_c) const_buf.resize(8 * cap_c);
-            rc = pfl_lower(R->packed_nodes.data(), d.nodes.size(), R->pool.data(), R->pool.size() / 8,
-                           roots2.data(), d.roots.size(), forced.empty() ? nullptr : forced.data(),
-                           d.forced.size(), tries[ti], code_buf.data(), cap_i, &ni, const_buf.data(),
-                           cap_c, &nc);
-            if (rc != -3) break;
-            cap_i *= 4;
-            cap_c *= 4;
-        }
-        if (rc == 0) {
-            R->code.assign(code_buf.begin(), code_buf.begin() + 4 * ni);
-            R->consts.assign(const_buf.begin(), const_buf.begin() + 8 * nc);
-            size_t n_spill = 0;
-            for (size_t i = 0; i < ni; i++) {
-                const uint32_t op = R->code[4 * i] & 0xffu;
-                n_spill += op == PF_W_SPILL || op == PF_W_FILL;
-            }
-            R->n_wregs = tries[ti];
-            if (ti == 0 && 8 * n_spill > ni) {  // spill-heavy: try the wide register file
-                have_narrow = true;
-                n_code.swap(R->code);
-                n_consts.swap(R->consts);
-                n_spill_narrow = n_spill;
-                continue;
-            }
-            if (ti == 1 && have_narrow && 2 * n_spill > n_spill_narrow) {
-                R->code.swap(n_code);
-                R->consts.swap(n_consts);
-                R->n_wregs = tries[0];
-            }
-            break;
-        }
-        if (ti == 1 && have_narrow) {  // the wide lowering failed (any rc): keep the narrow one
-            R->code.swap(n_code);
-            R->consts.swap(n_consts);
-            R->n_wregs = tries[0];
-            rc = 0;
-            break;
-        }
-        if (rc != -2) break;
-    }
-    if (rc != 0) {
-        t_err = pfl_last_error();
-        throw TermError{rc};
     }
 }
 
@@ -1814,401 +1326,6 @@ Result* lower_job(const Store& S, const std::vector<uint32_t>& rs, const Parents
     return R;
 }
 
-// ---- config-3 synthetic DAGs natively (synth.random_dag_set, bit for bit) ------------------
-// numpy's Philox4x64-10 bit generator and the Generator draws random_dag_set makes: random()
-// (53-bit double from next_uint64), integers(lo, hi) for int64 (Lemire on next_uint32, which
-// uses both halves of a 64-bit output in turn) and integers(0, 2^32, size=8, dtype=uint64)
-// (eight next_uint32).  Checked against numpy draw for draw (tests/test_synth_native.py).
-struct NpPhilox {
-    uint64_t ctr[4] = {0, 0, 0, 0}, key[2], buf[4] = {0, 0, 0, 0};
-    int pos = 4;
-    bool has32 = false;
-    uint32_t u32 = 0;
-
-    explicit NpPhilox(unsigned __int128 k) {
-        key[0] = (uint64_t)k;
-        key[1] = (uint64_t)(k >> 64);
-    }
-    static void mulhilo(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
-        const unsigned __int128 p = (unsigned __int128)a * b;
-        *hi = (uint64_t)(p >> 64);
-        *lo = (uint64_t)p;
-    }
-    uint64_t next64() {
-        if (pos < 4) return buf[pos++];
-        if (++ctr[0] == 0 && ++ctr[1] == 0 && ++ctr[2] == 0) ++ctr[3];
-        uint64_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k0 = key[0], k1 = key[1];
-        for (int r = 0; r < 10; r++) {
-            uint64_t hi0, lo0, hi1, lo1;
-            mulhilo(0xD2E7470EE14C6C93ull, c[0], &hi0, &lo0);
-            mulhilo(0xCA5A826395121157ull, c[2], &hi1, &lo1);
-            const uint64_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-            c[0] = n0;
-            c[1] = lo1;
-            c[2] = n2;
-            c[3] = lo0;
-            k0 += 0x9E3779B97F4A7C15ull;
-            k1 += 0xBB67AE8584CAA73Bull;
-        }
-        for (int i = 0; i < 4; i++) buf[i] = c[i];
-        pos = 1;
-        return buf[0];
-    }
-    uint32_t next32() {
-        if (has32) {
-            has32 = false;
-            return u32;
-        }
-        const uint64_t v = next64();
-        has32 = true;
-        u32 = (uint32_t)(v >> 32);
-        return (uint32_t)v;
-    }
-    double random() { return (double)(next64() >> 11) * (1.0 / 9007199254740992.0); }
-    int64_t integers(int64_t lo, int64_t hi) {  // [lo, hi), range < 2^32
-        const uint64_t rng = (uint64_t)(hi - lo - 1);
-        if (rng == 0) return lo;
-        if (rng == 0xFFFFFFFFull) return lo + next32();
-        const uint32_t rexcl = (uint32_t)rng + 1u;
-        uint64_t m = (uint64_t)next32() * rexcl;
-        uint32_t left = (uint32_t)m;
-        if (left < rexcl) {
-            const uint32_t thr = (uint32_t)((0xFFFFFFFFull - rng) % rexcl);
-            while (left < thr) {
-                m = (uint64_t)next32() * rexcl;
-                left = (uint32_t)m;
-            }
-        }
-        return lo + (int64_t)(m >> 32);
-    }
-};
-
-// 256-bit values as C8 (little-endian u32 limbs): the planted-value arithmetic of synth._eval
-bool c8_zero(const C8& a) {
-    for (int i = 0; i < 8; i++)
-        if (a.l[i]) return false;
-    return true;
-}
-bool c8_ult(const C8& a, const C8& b) {
-    for (int i = 7; i >= 0; i--)
-        if (a.l[i] != b.l[i]) return a.l[i] < b.l[i];
-    return false;
-}
-C8 c8_add(const C8& a, const C8& b) {
-    C8 r;
-    uint64_t c = 0;
-    for (int i = 0; i < 8; i++) {
-        c += (uint64_t)a.l[i] + b.l[i];
-        r.l[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    return r;
-}
-C8 c8_not(const C8& a) {
-    C8 r;
-    for (int i = 0; i < 8; i++) r.l[i] = ~a.l[i];
-    return r;
-}
-C8 c8_neg(const C8& a) { return c8_add(c8_not(a), c8_small(1, 256)); }
-C8 c8_sub(const C8& a, const C8& b) { return c8_add(a, c8_neg(b)); }
-uint32_t c8_bitlen(const C8& a) {
-    for (int i = 7; i >= 0; i--)
-        if (a.l[i]) return 32u * (uint32_t)i + 32u - (uint32_t)__builtin_clz(a.l[i]);
-    return 0;
-}
-C8 c8_shl(const C8& a, uint32_t k) {  // k < 256
-    C8 r;
-    const uint32_t q = k / 32, s = k % 32;
-    for (int i = 7; i >= 0; i--) {
-        const int j = i - (int)q;
-        uint32_t v = j >= 0 ? a.l[j] << s : 0u;
-        if (s && j - 1 >= 0) v |= a.l[j - 1] >> (32 - s);
-        r.l[i] = v;
-    }
-    return r;
-}
-C8 c8_lshr(const C8& a, uint32_t k, uint32_t fill = 0u) {  // k < 256; fill: 0 or ~0u
-    C8 r;
-    const uint32_t q = k / 32, s = k % 32;
-    for (int i = 0; i < 8; i++) {
-        const uint32_t j = (uint32_t)i + q;
-        const uint32_t lo = j < 8 ? a.l[j] : fill, hi = j + 1 < 8 ? a.l[j + 1] : fill;
-        r.l[i] = s ? (lo >> s) | (hi << (32 - s)) : lo;
-    }
-    return r;
-}
-// a / b and a % b (b != 0): Knuth's algorithm D on 32-bit digits (Hacker's Delight divmnu)
-void c8_divrem(const C8& a, const C8& b, C8* q, C8* r) {
-    memset(q, 0, sizeof(C8));
-    memset(r, 0, sizeof(C8));
-    int m = 8, n = 8;
-    while (m > 0 && a.l[m - 1] == 0) m--;
-    while (n > 0 && b.l[n - 1] == 0) n--;
-    if (m < n) {
-        *r = a;
-        return;
-    }
-    if (n == 1) {
-        uint64_t k = 0;
-        for (int j = m - 1; j >= 0; j--) {
-            const uint64_t cur = (k << 32) | a.l[j];
-            q->l[j] = (uint32_t)(cur / b.l[0]);
-            k = cur - (uint64_t)q->l[j] * b.l[0];
-        }
-        r->l[0] = (uint32_t)k;
-        return;
-    }
-    const int s = __builtin_clz(b.l[n - 1]);
-    uint32_t vn[8], un[9];
-    for (int i = n - 1; i > 0; i--) vn[i] = (b.l[i] << s) | (s ? (uint32_t)((uint64_t)b.l[i - 1] >> (32 - s)) : 0u);
-    vn[0] = b.l[0] << s;
-    un[m] = s ? (uint32_t)((uint64_t)a.l[m - 1] >> (32 - s)) : 0u;
-    for (int i = m - 1; i > 0; i--) un[i] = (a.l[i] << s) | (s ? (uint32_t)((uint64_t)a.l[i - 1] >> (32 - s)) : 0u);
-    un[0] = a.l[0] << s;
-    const uint64_t base = 1ull << 32;
-    for (int j = m - n; j >= 0; j--) {
-        const uint64_t num = ((uint64_t)un[j + n] << 32) | un[j + n - 1];
-        uint64_t qhat = num / vn[n - 1], rhat = num - qhat * vn[n - 1];
-        while (qhat >= base || qhat * vn[n - 2] > ((rhat << 32) | un[j + n - 2])) {
-            qhat--;
-            rhat += vn[n - 1];
-            if (rhat >= base) break;
-        }
-        int64_t borrow = 0;
-        for (int i = 0; i < n; i++) {
-            const uint64_t p = qhat * vn[i];
-            const int64_t t = (int64_t)un[i + j] - borrow - (int64_t)(p & 0xFFFFFFFFull);
-            un[i + j] = (uint32_t)t;
-            borrow = (int64_t)(p >> 32) - (t >> 32);
-        }
-        const int64_t t = (int64_t)un[j + n] - borrow;
-        un[j + n] = (uint32_t)t;
-        q->l[j] = (uint32_t)qhat;
-        if (t < 0) {
-            q->l[j]--;
-            uint64_t c = 0;
-            for (int i = 0; i < n; i++) {
-                c += (uint64_t)un[i + j] + vn[i];
-                un[i + j] = (uint32_t)c;
-                c >>= 32;
-            }
-            un[j + n] += (uint32_t)c;
-        }
-    }
-    for (int i = 0; i < n; i++) r->l[i] = (un[i] >> s) | (s ? (uint32_t)((uint64_t)un[i + 1] << (32 - s)) : 0u);
-}
-// a * b mod 2^256 on 64-bit limbs (10 products)
-C8 c8_mul64(const C8& a, const C8& b) {
-    uint64_t x[4], y[4], r[4] = {0, 0, 0, 0};
-    memcpy(x, a.l, 32);
-    memcpy(y, b.l, 32);
-    for (int i = 0; i < 4; i++) {
-        unsigned __int128 c = 0;
-        for (int j = 0; i + j < 4; j++) {
-            c += (unsigned __int128)x[i] * y[j] + r[i + j];
-            r[i + j] = (uint64_t)c;
-            c >>= 64;
-        }
-    }
-    C8 out;
-    memcpy(out.l, r, 32);
-    return out;
-}
-C8 c8_pow(const C8& b, const C8& e) {  // b^e mod 2^256 (pow(a, b, 1 << 256))
-    const uint32_t n = c8_bitlen(e);
-    if (!(b.l[0] & 1u) && n > 8) return c8_small(0, 256);   // even base, e >= 256: 2^256 | b^e
-    C8 r = c8_small(1, 256), x = b;
-    for (uint32_t i = 0; i < n; i++) {
-        if ((e.l[i / 32] >> (i % 32)) & 1u) r = c8_mul64(r, x);
-        if (i + 1 < n) x = c8_mul64(x, x);
-    }
-    return r;
-}
-bool c8_neg_sign(const C8& a) { return a.l[7] >> 31; }
-C8 c8_abs(const C8& a) { return c8_neg_sign(a) ? c8_neg(a) : a; }
-bool c8_slt(const C8& a, const C8& b) {
-    const bool sa = c8_neg_sign(a), sb = c8_neg_sign(b);
-    if (sa != sb) return sa;
-    return c8_ult(a, b);
-}
-
-C8 synth_eval(uint32_t op, const C8& a, const C8& b) {  // synth._eval at w = 256
-    C8 q, r;
-    switch (op) {
-        case PF_W_ADD: return c8_add(a, b);
-        case PF_W_SUB: return c8_sub(a, b);
-        case PF_W_MUL: return c8_mul64(a, b);
-        case PF_W_UDIV:
-            if (c8_zero(b)) return c8_not(c8_small(0, 256));
-            c8_divrem(a, b, &q, &r);
-            return q;
-        case PF_W_UREM:
-            if (c8_zero(b)) return a;
-            c8_divrem(a, b, &q, &r);
-            return r;
-        case PF_W_SDIV:
-        case PF_W_SREM: {
-            const bool sa = c8_neg_sign(a), sb = c8_neg_sign(b);
-            if (c8_zero(b)) return op == PF_W_SDIV ? (sa ? c8_small(1, 256) : c8_not(c8_small(0, 256))) : a;
-            c8_divrem(c8_abs(a), c8_abs(b), &q, &r);
-            if (op == PF_W_SDIV) return sa == sb ? q : c8_neg(q);
-            return sa ? c8_neg(r) : r;
-        }
-        case PF_W_AND: { C8 z; for (int i = 0; i < 8; i++) z.l[i] = a.l[i] & b.l[i]; return z; }
-        case PF_W_OR: { C8 z; for (int i = 0; i < 8; i++) z.l[i] = a.l[i] | b.l[i]; return z; }
-        case PF_W_XOR: { C8 z; for (int i = 0; i < 8; i++) z.l[i] = a.l[i] ^ b.l[i]; return z; }
-        case PF_W_NOT: return c8_not(a);
-        case PF_W_SHL: return c8_bitlen(b) > 8 ? c8_small(0, 256) : c8_shl(a, b.l[0]);
-        case PF_W_LSHR: return c8_bitlen(b) > 8 ? c8_small(0, 256) : c8_lshr(a, b.l[0]);
-        case PF_W_ASHR: {
-            const uint32_t fill = c8_neg_sign(a) ? ~0u : 0u;
-            if (c8_bitlen(b) > 8) {
-                C8 z;
-                for (int i = 0; i < 8; i++) z.l[i] = fill;
-                return z;
-            }
-            return c8_lshr(a, b.l[0], fill);
-        }
-        case PF_W_EXP: return c8_pow(a, b);
-        default: return a;
-    }
-}
-
-constexpr uint64_t kDagGenSeed = 20260101ull;
-constexpr uint32_t kCandSeedBase = 0x4D595448u;
-// synth._MIX in order (the op kinds) and its normalised cumulative probabilities, the doubles
-// numpy's cumsum / cdf[-1] produces (tests/test_synth_native.py checks the table)
-enum SynthKind { SK_MUL, SK_DIV, SK_REM, SK_EXP, SK_ADDSUB, SK_LOGIC, SK_SHIFT, SK_ITECMP };
-
-C8 synth_leaf_value(NpPhilox& g) {  // synth._leaf_value
-    if (g.random() < 0.5) {  // _rand256: eight u32 draws, the first the most significant
-        C8 v;
-        for (int i = 7; i >= 0; i--) v.l[i] = g.next32();
-        return v;
-    }
-    const int64_t j = g.integers(0, 9);
-    switch (j) {
-        case 0: return c8_small(0, 256);
-        case 1: return c8_small(1, 256);
-        case 2: return c8_small(2, 256);
-        case 3: return c8_not(c8_small(0, 256));
-        case 4: { C8 v = c8_small(0, 256); v.l[7] = 0x80000000u; return v; }
-        case 5: { C8 v = c8_small(0, 256); for (int i = 0; i < 5; i++) v.l[i] = ~0u; return v; }
-        default: {
-            const int64_t k = g.integers(0, 256);
-            C8 p = c8_small(0, 256);
-            p.l[k / 32] = 1u << (k % 32);
-            if (j == 6) return c8_sub(p, c8_small(1, 256));
-            if (j == 8) return c8_add(p, c8_small(1, 256));
-            return p;
-        }
-    }
-}
-
-// One config-3 DAG into R (synth.random_dag_set(dag_id, plant)); the witness into *wit.
-void synth_dag(uint32_t dag_id, bool plant, const double* cdf, Result* R, std::vector<C8>* wit) {
-    NpPhilox g(((unsigned __int128)kDagGenSeed << 32) | dag_id);
-    Dag d(256);
-    const int64_t n_vars = g.integers(4, 9);
-    wit->clear();
-    for (int64_t v = 0; v < n_vars; v++) wit->push_back(synth_leaf_value(g));
-    std::vector<std::pair<int32_t, C8>> leaves, interior;
-    for (int64_t v = 0; v < n_vars; v++) {
-        bool created;
-        leaves.push_back({d.var("x" + std::to_string(v), 256, PF_VK_GENERIC, 0, 0, plant, (*wit)[v], &created),
-                          (*wit)[v]});
-    }
-    for (int k = 0; k < 4; k++) {
-        const C8 c = synth_leaf_value(g);
-        leaves.push_back({d.cnst(c, 256), c});
-    }
-    const int depth = 32, window = 6;
-    auto pick = [&](bool first) -> std::pair<int32_t, C8> {
-        if (first && !interior.empty() && (int)interior.size() <= depth) return interior.back();
-        const size_t np = std::min<size_t>(interior.size(), (size_t)window);
-        if (np && g.random() < 0.6) return interior[interior.size() - np + (size_t)g.integers(0, (int64_t)np)];
-        return leaves[(size_t)g.integers(0, (int64_t)leaves.size())];
-    };
-    for (int it = 0; it < 48; it++) {
-        const double u = g.random();
-        int kind = 0;
-        while (kind < 7 && !(u < cdf[kind])) kind++;   // bisect_right
-        auto A = pick(true);
-        auto B = pick(false);
-        uint32_t op = 0;
-        switch (kind) {
-            case SK_DIV: op = g.random() < 0.5 ? PF_W_UDIV : PF_W_SDIV; break;
-            case SK_REM: op = g.random() < 0.5 ? PF_W_UREM : PF_W_SREM; break;
-            case SK_ADDSUB: op = g.random() < 0.5 ? PF_W_ADD : PF_W_SUB; break;
-            case SK_LOGIC: {
-                static const uint32_t ops[4] = {PF_W_AND, PF_W_OR, PF_W_XOR, PF_W_NOT};
-                op = ops[g.integers(0, 4)];
-                break;
-            }
-            case SK_SHIFT: {
-                static const uint32_t ops[3] = {PF_W_SHL, PF_W_LSHR, PF_W_ASHR};
-                op = ops[g.integers(0, 3)];
-                if (g.random() < 0.5) {
-                    (void)g.integers(0, 256);   // drawn and unused, as in synth.py
-                    B.first = d.op(PF_W_AND, 256, {B.first, d.cnst(0xFF, 256)});
-                    C8 m = c8_small(0, 256);
-                    m.l[0] = B.second.l[0] & 0xFFu;
-                    B.second = m;
-                }
-                break;
-            }
-            case SK_ITECMP: {
-                static const uint32_t ops[3] = {PF_B_ULT, PF_B_SLT, PF_B_EQ};
-                const uint32_t c_op = ops[g.integers(0, 3)];
-                auto C2 = pick(false);
-                const int32_t cond = d.op(c_op, 256, {A.first, C2.first});
-                const bool cv = c_op == PF_B_ULT ? c8_ult(A.second, C2.second)
-                                : c_op == PF_B_EQ ? A.second == C2.second : c8_slt(A.second, C2.second);
-                const int32_t node = d.op(PF_W_ITE, 256, {cond, A.first, B.first});
-                interior.push_back({node, cv ? A.second : B.second});
-                continue;
-            }
-            case SK_MUL: op = PF_W_MUL; break;
-            default: op = PF_W_EXP; break;
-        }
-        int32_t node;
-        C8 val;
-        if (op == PF_W_NOT) {
-            node = d.op(op, 256, {A.first});
-            val = c8_not(A.second);
-        } else {
-            node = d.op(op, 256, {A.first, B.first});
-            val = synth_eval(op, A.second, B.second);
-        }
-        interior.push_back({node, val});
-    }
-    const int64_t n_roots = g.integers(2, 5);
-    const size_t nt = std::min<size_t>(interior.size(), (size_t)std::max<int64_t>(n_roots * 2, 8));
-    const size_t t0 = interior.size() - nt;
-    for (int64_t r = 0; r < n_roots; r++) {
-        const auto& NV = interior[t0 + (size_t)g.integers(0, (int64_t)nt)];
-        const int64_t cmp = g.integers(0, 3);
-        int32_t root;
-        if (cmp == 0) {
-            root = d.op(PF_B_EQ, 256, {NV.first, d.cnst(NV.second, 256)});
-        } else if (cmp == 1) {
-            root = d.op(PF_B_ULE, 256, {NV.first, d.cnst(NV.second, 256)});
-        } else {
-            const int32_t c = d.cnst(NV.second, 256);
-            root = d.op(PF_B_ULE, 256, {c, NV.first});
-        }
-        d.roots.push_back(root);
-    }
-    emit_program(d, R);
-    for (const DVar& v : d.vars) {
-        R->names += v.name;
-        R->names.push_back('\0');
-    }
-    R->parented = plant;
-    R->dag = std::move(d);
-    R->dag.memo.clear();
-}
-
 }  // namespace
 
 extern "C" {
@@ -2228,31 +1345,6 @@ void* pflt_store_new(void) {
 }
 
 uint32_t pflt_features(void) { return PFLT_FEAT_EXPLICIT | PFLT_FEAT_SYNTH; }
-
-int pflt_synth(uint32_t first_id, size_t n, uint32_t plant, const double* cdf, void** results,
-               uint32_t* witness_limbs, uint32_t* n_vars_out) {
-    try {
-        std::vector<C8> wit;
-        for (size_t i = 0; i < n; i++) {
-            Result* R = new Result();
-            results[i] = R;
-            try {
-                synth_dag(first_id + (uint32_t)i, plant != 0, cdf, R, &wit);
-            } catch (const TermError& e) {
-                R->rc = e.rc;
-                R->err = t_err;
-                return -1;
-            }
-            if (n_vars_out) n_vars_out[i] = (uint32_t)wit.size();
-            if (witness_limbs)
-                for (size_t v = 0; v < wit.size(); v++) memcpy(witness_limbs + 64 * i + 8 * v, wit[v].l, 32);
-        }
-    } catch (const std::exception& e) {
-        t_err = std::string("pflt_synth: ") + e.what();
-        return -1;
-    }
-    return 0;
-}
 
 void pflt_store_free(void* st) { delete (Store*)st; }
 
@@ -2314,18 +1406,6 @@ uint32_t key_id(Store* S, const std::string& k) {
     S->key_names.push_back(k);
     S->key_ids.emplace(k, id);
     return id;
-}
-
-bool keccak_app(const std::string& f, std::string* n, bool* inv) {  // ^keccak256_(\d+)(-1)?$
-    static const char pre[] = "keccak256_";
-    if (f.compare(0, sizeof(pre) - 1, pre) != 0) return false;
-    size_t i = sizeof(pre) - 1, j = i;
-    while (j < f.size() && isdigit((unsigned char)f[j])) j++;
-    if (j == i) return false;
-    *n = f.substr(i, j - i);
-    if (j == f.size()) { *inv = false; return true; }
-    if (f.compare(j, std::string::npos, "-1") == 0) { *inv = true; return true; }
-    return false;
 }
 
 void merge_sorted(std::vector<uint32_t>* into, const std::vector<uint32_t>& b) {

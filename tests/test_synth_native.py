@@ -1,6 +1,7 @@
-"""The native config-3 generator (pflt_synth, csrc/pf_terms.cpp) against synth.random_dag_set:
-numpy's Philox Generator stream, the DAG builder, the planted values and the lowering restated
-in C++ must give the same packed batch, DAG for DAG, unplanted and planted."""
+"""The native config-3 generator (pflt_synth, csrc/pf_synth.cpp) against synth.random_dag_set:
+numpy's Philox Generator stream and the DAG builder restated in C++, the planted values from the
+host evaluator (csrc/pf_hostint.h eval_op, against synth._eval here) and the lowering must give
+the same packed batch, DAG for DAG, unplanted and planted."""
 
 import numpy as np
 import pytest

@@ -16,7 +16,10 @@ register >= PF_NW_NARROW and runs the 16-register search kernels.
 
 Every builder returns a Program with two extra attributes: ``verdict`` (what the caller said
 the program evaluates to under its assignment) and ``assignment`` (the variable values, for
-``parents=False`` sets that are evaluated with explicit candidates instead)."""
+``parents=False`` sets that are evaluated with explicit candidates instead).
+
+bool_file_cases.py builds on ``Asm`` for the Bool side: the B register file, B spills and
+asserts fused into B-unit ops (test_bool_file_cases.py, test_gpu_bool_file.py)."""
 
 from mythril_amd import ir
 

@@ -36,16 +36,17 @@ def device_program(batch):
     return out[:n.value], dout
 
 
-def eval_device(sv, code_rows, values):
+def eval_device(sv, code_rows, values, hook=None):
     """SetView.evaluate with the device flags: a KA / KB operand is const[a] / const[b], an
     FA / FB operand the previous instruction's W result (held here in spare register slots);
     a W result whose PF_TR_WW is cleared is not written back (its register keeps its old
     value, or none: a later read of it fails here); a PF_I_ASSERT op also asserts its B
-    result."""
+    result.  ``hook(i, B)``, when given, runs after row i's own effect and before its fused
+    assert, and may change the B file (the mutations of tests/test_bool_file_cases.py)."""
     W, B, S = {}, {}, {}
     root = True
     last = None
-    for (w0, w1, aux0, aux1) in code_rows:
+    for i, (w0, w1, aux0, aux1) in enumerate(code_rows):
         op = w0 & 0xFF
         if op == O.OP["END"]:
             break
@@ -73,6 +74,8 @@ def eval_device(sv, code_rows, values):
                     del W[d]
                 else:
                     W[d] = old
+        if hook is not None:
+            hook(i, B)
         if w0 & I_ASSERT:
             root = root and B[w1 & 0xFF]
     return root

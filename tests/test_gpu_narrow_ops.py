@@ -8,7 +8,10 @@ An explicit assignment reaches a search kernel by the candidate-0 protocol (op_p
 parents on every variable, ``budget=1``, ``found == 0`` iff the program holds.  ``base`` chooses
 the register file (0: registers 0..6, the narrow kernels; 8: registers 8..14, the r16 kernels),
 ``flags`` the EARLY template constant.  Every row is also uploaded with its expectation
-corrupted in one bit, and that copy must come out NOT_FOUND."""
+corrupted in one bit, and that copy must come out NOT_FOUND.
+
+test_bool_ops here runs the B ops in five B registers of lane 0; test_gpu_bool_file.py covers the
+whole B file, every lane, B spills and fused asserts."""
 
 import functools
 

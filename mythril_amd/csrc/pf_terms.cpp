@@ -307,8 +307,8 @@ struct Lowering {
     }
 
     int32_t mkvar(const std::string& name, uint32_t w, const VarTerm& term, const C8* parent,
-                  const std::pair<uint32_t, uint32_t>* read) {
-        const uint32_t kind = var_kind(name, w);
+                  const std::pair<uint32_t, uint32_t>* read, bool generic = false) {
+        const uint32_t kind = generic ? (uint32_t)PF_VK_GENERIC : var_kind(name, w);
         uint32_t h0 = 0, h1 = 0;
         if (kind == PF_VK_ACTOR) {
             if (!actors_forced) {
@@ -712,13 +712,8 @@ struct Lowering {
             case T_EQ: {
                 const uint32_t a = r.args[0], bt = r.args[1];
                 if (width(a) > 256 || width(bt) > 256) {
-                    const Chunks ca = chunks(a), cb = chunks(bt);
-                    int32_t acc = -1;
-                    for (size_t i = 0; i < std::min(ca.size(), cb.size()); i++) {
-                        const int32_t e = d.op(PF_B_EQ, ca[i].second, {ca[i].first, cb[i].first});
-                        acc = acc < 0 ? e : d.op(PF_B_AND, 1, {acc, e});
-                    }
-                    return acc;
+                    const Chunks ca = chunks(a);
+                    return eq_chunks(ca, chunks(bt), false);
                 }
                 const int32_t x = node(a);
                 return d.op(PF_B_EQ, width(a), {x, node(bt)});
@@ -734,6 +729,38 @@ struct Lowering {
             return d.op(opc, width(a), {x, node(bt)});
         }
         lerr("unsupported bool op %s", r.name.c_str());
+    }
+
+    // TermLowering._eq_chunks: the per-chunk B_EQ under B_AND.  With decide (array indices) a
+    // pair of chunks that is one node is left out and a pair of different constants settles
+    // it: EQ_TRUE / EQ_FALSE when no compare is left to emit
+    static constexpr int32_t EQ_TRUE = -1, EQ_FALSE = -2;
+    int32_t eq_chunks(const Chunks& A, const Chunks& B, bool decide) {
+        int32_t acc = -1;
+        for (size_t i = 0; i < std::min(A.size(), B.size()); i++) {
+            const int32_t x = A[i].first, y = B[i].first;
+            if (decide) {
+                if (x == y) continue;
+                if (d.cval(x) && d.cval(y)) return EQ_FALSE;  // hash-consed: different values
+            }
+            const int32_t e = d.op(PF_B_EQ, A[i].second, {x, y});
+            acc = acc < 0 ? e : d.op(PF_B_AND, 1, {acc, e});
+        }
+        return acc;
+    }
+
+    // TermLowering._concat_apart: two concats with the same part widths and, at some position,
+    // two different constants are never equal
+    bool concat_apart(uint32_t a, uint32_t bt) const {
+        const TermRec &x = T(a), &y = T(bt);
+        if (x.op != T_CONCAT || y.op != T_CONCAT || x.args.size() != y.args.size()) return false;
+        for (size_t i = 0; i < x.args.size(); i++)
+            if (width(x.args[i]) != width(y.args[i])) return false;
+        for (size_t i = 0; i < x.args.size(); i++) {
+            const TermRec &p = T(x.args[i]), &q = T(y.args[i]);
+            if (p.op == T_BV && q.op == T_BV && x.args[i] != y.args[i]) return true;
+        }
+        return false;
     }
 
     // ---- arrays -----------------------------------------------------------------------
@@ -791,6 +818,15 @@ struct Lowering {
         if (A.op == T_STORE) {
             const uint32_t base = A.args[0], k = A.args[1], v = A.args[2];
             if (k == idx) return node(v);
+            if (width(idx) > 256) {
+                if (concat_apart(k, idx)) return select(base, idx);
+                const int32_t rest = select(base, idx);
+                const Chunks ci = chunks(idx);
+                const int32_t c = eq_chunks(ci, chunks(k), true);
+                if (c == EQ_FALSE) return rest;
+                if (c == EQ_TRUE) return node(v);
+                return d.op(PF_W_ITE, A.w2, {c, node(v), rest});
+            }
             const auto kf = offset_form(k), xf = offset_form(idx);
             if (kf.first == xf.first)  // the same base: the offsets decide
                 return kf.second == xf.second ? node(v) : select(base, idx);
@@ -808,7 +844,6 @@ struct Lowering {
         if (A.op != T_ARRAY) lerr("select over %s", A.name.c_str());
         const std::string& name = A.name;
         const uint32_t rng = A.w2;
-        if (width(idx) > 256) lerr("array index wider than 256 bits");
         if (explicit_) return leaf_read(arr, idx, rng);
         auto it = arrays.find(name);
         if (it == arrays.end()) {
@@ -817,6 +852,9 @@ struct Lowering {
         }
         for (const auto& e : it->second)
             if ((uint32_t)e[0] == idx) return e[3];
+        if (!it->second.empty() && width((uint32_t)it->second[0][0]) != width(idx))
+            lerr("array %s read at two index widths", name.c_str());
+        if (width(idx) > 256) return select_wide(arr, idx);
         const int32_t inode = node(idx);
         std::string vname;
         if (T(idx).op == T_BV) {
@@ -852,6 +890,34 @@ struct Lowering {
         }
         val = index_run(run, run_base, idx, inode, rng, val);
         entries.push_back({(int32_t)idx, (int32_t)arr, inode, val});
+        return val;
+    }
+
+    // TermLowering._select_wide: a base array read at an index of more than 256 bits — the
+    // index carried as chunks (wide_index, where a narrow entry keeps its node), a generic
+    // variable whatever its name, the plain ite chain
+    std::unordered_map<uint32_t, Chunks> wide_index;
+    int32_t select_wide(uint32_t arr, uint32_t idx) {
+        const std::string& name = T(arr).name;
+        const uint32_t rng = T(arr).w2;
+        auto& entries = arrays[name];
+        const Chunks ich = chunks(idx);
+        std::string vname;
+        if (T(idx).op == T_BV)
+            vname = name + "[" + big_decimal(T(idx).val) + "]";
+        else
+            vname = name + "@" + std::to_string(entries.size());
+        const std::pair<uint32_t, uint32_t> rd{arr, idx};
+        int32_t val = mkvar(vname, rng, VarTerm{PFLT_VT_SELECT, arr, idx, 0}, nullptr, &rd, true);
+        for (size_t i = entries.size(); i-- > 0;) {
+            const auto& e = entries[i];
+            if (concat_apart((uint32_t)e[0], idx)) continue;
+            const int32_t c = eq_chunks(ich, wide_index[(uint32_t)e[0]], true);
+            if (c == EQ_FALSE) continue;
+            val = c == EQ_TRUE ? e[3] : d.op(PF_W_ITE, rng, {c, e[3], val});
+        }
+        wide_index[idx] = ich;
+        entries.push_back({(int32_t)idx, (int32_t)arr, -1, val});
         return val;
     }
 

@@ -28,7 +28,11 @@ Values wider than 256 bits are carried as 256-bit chunks: keccak256_512 inputs, 
 sum's carry (bitvec_helper.py:199-213, used by every IntegerArithmetics query,
 integer.py:144-158).  Chunked ops: concat / zero_extend / extract (across chunks) / ite /
 add / sub (carry rippled as a B value) / neg / and / or / xor / not / shifts by a constant /
-= / unsigned and signed orderings.  Anything else raises LoweringError -> z3.
+= / unsigned and signed orderings / array reads with indices of 257-512 bits (EIP-1153
+transient storage: ``K(512 -> 256, 0)`` stored and read at ``Concat(address, slot)``,
+state/transient_storage.py:21-50 — "index == key" is the chunked ``=``, and two concats
+whose parts at one position are different constants are never compared at all).  Anything
+else raises LoweringError -> z3.
 """
 
 from __future__ import annotations
@@ -113,7 +117,8 @@ class TermLowering:
         self.parent = parent or {}
         self.memo: Dict[T.Term, object] = {}
         self.var_terms: List[T.Term] = []
-        # base array name -> [(idx term, select term, idx node, value node)] in lookup order
+        # base array name -> [(idx term, select term, idx node (chunks for an index wider
+        # than 256 bits), value node)] in lookup order
         self.arrays: Dict[str, List[Tuple[T.Term, T.Term, int, object]]] = {}
         self.keccak_apps: Dict[int, List[Tuple[T.Term, object, object]]] = {}  # n -> [(arg term, arg val, f node)]
         self.inv_apps: Dict[int, List[Tuple[object, object]]] = {}  # n -> [(key node, value node)]
@@ -124,8 +129,10 @@ class TermLowering:
         self.power_facts: Dict[Tuple[int, int], int] = {}            # concrete (b, e) -> b^e
 
     # ---- leaves -----------------------------------------------------------------------
-    def _var(self, name: str, w: int, term: T.Term, parent: Optional[int] = None) -> int:
-        kind = var_kind(name, w)
+    def _var(self, name: str, w: int, term: T.Term, parent: Optional[int] = None,
+             kind: Optional[int] = None) -> int:
+        if kind is None:
+            kind = var_kind(name, w)
         hint0 = hint1 = 0
         if kind == ir.VK_ACTOR:
             hint0, hint1 = self._actor_table()
@@ -409,12 +416,7 @@ class TermLowering:
         if op == "=":
             a, b = t.args
             if a.width > 256 or b.width > 256:
-                ca, cb = self.chunks(a), self.chunks(b)
-                acc = None
-                for (x, wx), (y, wy) in zip(ca, cb):
-                    e = d.op(ir.B_EQ, wx, x, y)
-                    acc = e if acc is None else d.op(ir.B_AND, 1, acc, e)
-                return acc
+                return self._eq_chunks(self.chunks(a), self.chunks(b))
             return d.op(ir.B_EQ, a.width, self.node(a), self.node(b))
         if op in _BCMP:
             a, b = t.args
@@ -422,6 +424,24 @@ class TermLowering:
                 return self._wide_cmp(op, a, b)
             return d.op(_BCMP[op], a.width, self.node(a), self.node(b))
         raise LoweringError(f"unsupported bool op {op}")
+
+    def _eq_chunks(self, A, B, decide: bool = False):
+        """Equality of two chunked values: the per-chunk ``B_EQ`` under ``B_AND``.  With
+        ``decide`` (array indices) a pair of chunks that is one node is left out and a pair of
+        different constants settles it: the result is then True / False when no compare is
+        left to emit."""
+        d = self.dag
+        acc = None
+        for (x, wx), (y, _) in zip(A, B):
+            if decide:
+                if x == y:
+                    continue
+                cx, cy = d._cval(x), d._cval(y)
+                if cx is not None and cy is not None:   # hash-consed: different values
+                    return False
+            e = d.op(ir.B_EQ, wx, x, y)
+            acc = e if acc is None else d.op(ir.B_AND, 1, acc, e)
+        return True if acc is None and decide else acc
 
     def _bvar(self, t: T.Term) -> int:
         before = len(self.dag.vars)
@@ -460,6 +480,16 @@ class TermLowering:
             base, k, v = arr.args
             if k is idx:
                 return self.node(v)
+            if idx.width > 256:
+                if self._concat_apart(k, idx):
+                    return self._select(base, idx, term)
+                rest = self._select(base, idx, T.select(base, idx))
+                c = self._eq_chunks(self.chunks(idx), self.chunks(k), decide=True)
+                if c is False:
+                    return rest
+                if c is True:
+                    return self.node(v)
+                return d.op(ir.W_ITE, arr.sort[2], c, self.node(v), rest)
             (kb, kc), (ib, ic) = self._offset_form(k), self._offset_form(idx)
             if kb is ib:  # the same base: the offsets decide (both constants: their values)
                 return self._select(base, idx, term) if kc != ic else self.node(v)
@@ -476,12 +506,14 @@ class TermLowering:
         if arr.op != "array":
             raise LoweringError(f"select over {arr.op}")
         name, rng = arr.val, arr.sort[2]
-        if idx.width > 256:
-            raise LoweringError("array index wider than 256 bits")
         entries = self.arrays.setdefault(name, [])
         for (it, _, _, val) in entries:
             if it is idx:
                 return val
+        if entries and entries[0][0].width != idx.width:
+            raise LoweringError(f"array {name} read at two index widths")
+        if idx.width > 256:
+            return self._select_wide(arr, idx, entries)
         inode = self.node(idx)
         if idx.op == "bv":
             vname = f"{name}[{idx.val}]"
@@ -511,6 +543,42 @@ class TermLowering:
             run.append((tc, inn, v))
         val = self._run(run, run_base, idx, inode, rng, val)
         entries.append((idx, sel_term, inode, val))
+        return val
+
+    @staticmethod
+    def _concat_apart(a: T.Term, b: T.Term) -> bool:
+        """Two concats with the same part widths and, at some position, two different
+        constants: never equal.  Transient storage keys are ``Concat(address, slot)`` with a
+        concrete address (transient_storage.py:50), so another contract's stores need no
+        test."""
+        if a.op != "concat" or b.op != "concat" or len(a.args) != len(b.args):
+            return False
+        if any(x.width != y.width for x, y in zip(a.args, b.args)):
+            return False
+        return any(x.op == "bv" and y.op == "bv" and x.val != y.val
+                   for x, y in zip(a.args, b.args))
+
+    def _select_wide(self, arr: T.Term, idx: T.Term, entries) -> int:
+        """A base array read at an index of more than 256 bits: the index is carried as
+        chunks (kept in the entry where a narrow read keeps its node), the variable is
+        generic whatever its name, and the lookup is the plain ``ite`` chain."""
+        d = self.dag
+        name, rng = arr.val, arr.sort[2]
+        ich = self.chunks(idx)
+        if idx.op == "bv":
+            vname = f"{name}[{idx.val}]"
+        else:
+            vname = f"{name}@{len(entries)}"
+        sel_term = T.select(arr, idx)
+        val = self._var(vname, rng, sel_term, kind=ir.VK_GENERIC)
+        for (it, _, ech, v) in reversed(entries):
+            if self._concat_apart(it, idx):
+                continue
+            c = self._eq_chunks(ich, ech, decide=True)
+            if c is False:
+                continue
+            val = v if c is True else d.op(ir.W_ITE, rng, c, v, val)
+        entries.append((idx, sel_term, ich, val))
         return val
 
     def _run(self, run, base, idx: T.Term, inode: int, rng: int, val):
@@ -694,11 +762,7 @@ class TermLowering:
             return d.bconst(False)
         if a.width <= 256:
             return d.op(ir.B_EQ, a.width, self.node(a), self.node(b))
-        acc = None
-        for (x, wx), (y, _) in zip(self.chunks(a), self.chunks(b)):
-            e = d.op(ir.B_EQ, wx, x, y)
-            acc = e if acc is None else d.op(ir.B_AND, 1, acc, e)
-        return acc
+        return self._eq_chunks(self.chunks(a), self.chunks(b))
 
     # ---- driver ---------------------------------------------------------------------------
     def lower(self, constraints: List[T.Term]) -> Lowered:
@@ -742,8 +806,6 @@ class ExplicitLowering(TermLowering):
 
     def _select(self, arr: T.Term, idx: T.Term, term: T.Term) -> int:
         if arr.op == "array":
-            if idx.width > 256:
-                raise LoweringError("array index wider than 256 bits")
             return self._leaf(T.select(arr, idx), arr.sort[2])
         return super()._select(arr, idx, term)
 

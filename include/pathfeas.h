@@ -142,6 +142,14 @@ int pf_climb_batch(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint3
                    uint32_t timeout_ms, const uint32_t* set_ids, size_t n,
                    uint32_t* status_out, uint32_t* score_out, uint32_t* round_out,
                    uint32_t* values_out, pf_stats* stats);
+/* pf_climb_batch with the candidates scored by `score` (enum pf_climb_score, include/pf_bytecode.h):
+ * PF_CLIMB_SCORE_SITES is pf_climb_batch itself, PF_CLIMB_SCORE_TREE carries distances through
+ * the Boolean structure above the compares.  Everything else — rounds, seeds, adoption, ties,
+ * PF_CLIMB_CUT, the outputs — is pf_climb_batch's.  An unknown score: error, nothing launched. */
+int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint32_t per_round,
+                          uint32_t score, uint32_t timeout_ms, const uint32_t* set_ids, size_t n,
+                          uint32_t* status_out, uint32_t* score_out, uint32_t* round_out,
+                          uint32_t* values_out, pf_stats* stats);
 
 /* Evaluate set `set` on n_cand explicit assignments, SoA limbs [var][limb][cand].          */
 int pf_eval_assignments(uint64_t handle, uint32_t set, const uint32_t* soa, uint32_t n_cand,

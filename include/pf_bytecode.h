@@ -331,6 +331,44 @@ enum pf_climb_status {
 #define PF_CLIMB_NEAR 256u
 #define PF_CLIMB_SEED_MUL 0x9E3779B97F4A7C15ull
 
+/* Scores (pf_climb_batch_scored).  PF_CLIMB_SCORE_SITES is the score above, and the default.
+ * Only how a candidate is scored differs between them: rounds, seeds, adoption, ties, candidate
+ * 0 from round 1 on, PF_CLIMB_CUT and "a witness is PF_CLIMB_HOLDS x sites and nothing else" are
+ * one contract.
+ *
+ * PF_CLIMB_SCORE_TREE, the tree score, carries distances through the Boolean structure above
+ * the compares, so that a failing OR / AND / NOT root is not flat.  On the device program, every
+ * B value carries two integers in 0..256 beside its bit: dt, how far it is from true, and df,
+ * how far from false; dt = 0 iff the bit is 1 and df = 0 iff the bit is 0.  With sat(x) =
+ * min(x, 256), the writer of B[d] sets (dt, df) to
+ *    PF_B_EQ             holds: (0, 1); fails: (popcount(a ^ b), 0)
+ *    PF_B_ULT, PF_B_ULE  D = bitlen(|a - b|) on the zero-extended register values;
+ *                        holds: (0, max(1, D)); fails: (max(1, D), 0)
+ *    PF_B_SLT, PF_B_SLE  the same on the values the kernel compares: a, b sign-extended from the
+ *                        width with the top bit (bit 255) flipped, an order-preserving map to
+ *                        unsigned
+ *    PF_B_UADD_NOOVF, PF_B_UMUL_NOOVF, PF_B_CONST
+ *                        no gradient: (0, 256) or (256, 0)
+ *    PF_B_VAR            (1 - bit, bit)
+ *    PF_B_NOT x          (df_x, dt_x)
+ *    PF_B_AND x y        (sat(dt_x + dt_y), min(df_x, df_y))
+ *    PF_B_OR x y         (min(dt_x, dt_y), sat(df_x + df_y))
+ *    PF_B_XOR x y        (min(sat(dt_x + df_y), sat(df_x + dt_y)),
+ *                         min(sat(dt_x + dt_y), sat(df_x + df_y)))
+ *    PF_B_ITE c x y      (min(sat(dt_c + dt_x), sat(df_c + dt_y)),
+ *                         min(sat(dt_c + df_x), sat(df_c + df_y)))
+ *    PF_B_SPILL, PF_B_FILL   the pair travels with the bit, for scratch slots and PF_SPILL_LDS
+ *                        entries alike
+ * A site — a PF_ASSERT, or any B op carrying PF_I_ASSERT — adds PF_CLIMB_HOLDS where it holds,
+ * else PF_CLIMB_NEAR - dt, which lies in 0..255.  So a failing fused PF_B_EQ adds exactly what
+ * it adds under PF_CLIMB_SCORE_SITES; a failing fused order compare adds the same too, except
+ * that a strict one on equal operands (D = 0) adds 255 where the sites score adds 256, and that
+ * the signed ones measure the distance on the sign-extended values.                          */
+enum pf_climb_score {
+    PF_CLIMB_SCORE_SITES = 0,
+    PF_CLIMB_SCORE_TREE = 1
+};
+
 /* flags for pf_check_batch */
 #define PF_FLAG_SHORTCIRCUIT 1u  /* stop a wave's set evaluation once all its lanes are false */
 #define PF_FLAG_EARLY_EXIT 2u    /* stop a set once any candidate satisfies it             */

@@ -67,6 +67,9 @@ SIGNATURES = {
     "pf_climb_batch": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint32, _u32p, _sz, _u32p, _u32p, _u32p, _u32p,
                                       ctypes.POINTER(pf_stats)]),
+    "pf_climb_batch_scored": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, ctypes.c_uint32, _u32p, _sz, _u32p, _u32p, _u32p,
+                                             _u32p, ctypes.POINTER(pf_stats)]),
     "pf_eval_assignments": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _u32p,
                                            ctypes.c_uint32, _u8p]),
     "pf_eval_program": (ctypes.c_int, [ctypes.c_int, _u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p,

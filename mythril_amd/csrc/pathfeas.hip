@@ -438,7 +438,7 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
 
 extern "C" {
 
-int pf_version(void) { return 2; }
+int pf_version(void) { return 3; }
 
 // Host only (no HIP call, tests/test_device_program.py): the program pf_batch_create would put
 // on the device — traffic / unit bits recomputed from the opcodes, then the fold pass (whatever
@@ -926,9 +926,19 @@ int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_id
 int pf_climb_batch(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint32_t per_round,
                    uint32_t timeout_ms, const uint32_t* set_ids, size_t n, uint32_t* status_out,
                    uint32_t* score_out, uint32_t* round_out, uint32_t* values_out, pf_stats* stats) {
+    return pf_climb_batch_scored(handle, global_seed, rounds, per_round, PF_CLIMB_SCORE_SITES, timeout_ms, set_ids,
+                                 n, status_out, score_out, round_out, values_out, stats);
+}
+
+int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint32_t per_round,
+                          uint32_t score, uint32_t timeout_ms, const uint32_t* set_ids, size_t n,
+                          uint32_t* status_out, uint32_t* score_out, uint32_t* round_out,
+                          uint32_t* values_out, pf_stats* stats) {
     std::lock_guard<std::mutex> lk(g_mu);
     Batch* B = as_batch(handle);
     if (!B) return fail("pf_climb_batch: null batch");
+    if (score != PF_CLIMB_SCORE_SITES && score != PF_CLIMB_SCORE_TREE)
+        return fail("pf_climb_batch: unknown score %u", score);
     if (rounds == 0) return fail("pf_climb_batch: rounds must be at least 1");
     if (per_round == 0) return fail("pf_climb_batch: per_round must be at least 1");
     if (n && !set_ids) return fail("pf_climb_batch: null set_ids");
@@ -1019,7 +1029,9 @@ int pf_climb_batch(uint64_t handle, uint64_t global_seed, uint32_t rounds, uint3
             const uint64_t items = (uint64_t)np * groups;
             const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early);
             const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
-            hipLaunchKernelGGL(part == 0 ? pf_climb_kernel : pf_climb_r16_kernel, dim3(blocks),
+            const auto kernel = score == PF_CLIMB_SCORE_TREE ? (part == 0 ? pf_climb_tree_kernel : pf_climb_tree_r16_kernel)
+                                                             : (part == 0 ? pf_climb_kernel : pf_climb_r16_kernel);
+            hipLaunchKernelGGL(kernel, dim3(blocks),
                                dim3(64 * PF_SEARCH_WG_WAVES), 0, st, descs_r, d_req + first, (uint32_t)np, B->d_code,
                                B->d_consts, schema_r, parents_r, gs, per_round, groups, r ? 1u : 0u, deadline, d_t0,
                                d_state, d_counters, d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);

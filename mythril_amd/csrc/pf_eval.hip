@@ -480,7 +480,14 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
 
 // MODE_CLIMB: MODE_GEN's candidates, no short-circuit, and the lane's score accumulated at the
 // assert sites (include/pf_bytecode.h, climb contract)
-enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2 };
+// MODE_CLIMB_TREE: MODE_CLIMB with the tree score (PF_CLIMB_SCORE_TREE): every B register carries
+// its two distances beside its bit, and a failing site adds PF_CLIMB_NEAR - dt
+enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2, MODE_CLIMB_TREE = 3 };
+
+// |a - b| of two 256-bit values taken as unsigned
+PF_INL u256 climb_absdiff(const u256& x, const u256& y) {
+    return pf::sel256(pf::ult256(x, y), pf::sub256(y, x), pf::sub256(x, y));
+}
 
 // Score of one fused compare-and-assert site (climb contract): PF_CLIMB_HOLDS where it holds,
 // else how near it is — EQ: PF_CLIMB_NEAR - popcount(a ^ b); ULT / ULE / SLT / SLE:
@@ -494,10 +501,48 @@ PF_INL uint32_t climb_term(uint32_t op, const u256& x, const u256& y, uint32_t h
         for (int i = 0; i < 8; i++) pc += (uint32_t)__builtin_popcount(x.l[i] ^ y.l[i]);
         near = PF_CLIMB_NEAR - pc;
     } else if (op >= PF_B_ULT && op <= PF_B_SLE) {
-        near = pf::clz256(pf::sel256(pf::ult256(x, y), pf::sub256(y, x), pf::sub256(x, y)));
+        near = pf::clz256(climb_absdiff(x, y));
     }
     return holds ? PF_CLIMB_HOLDS : near;
 }
+
+// Tree score (climb contract): a B value's distances, dt in the low and df in the high half of
+// one u32, both 0..256.  Everything below is selects on per-lane values; the opcodes that
+// choose between the forms are wave-uniform.
+PF_INL uint32_t tree_pair(uint32_t dt, uint32_t df) { return dt | (df << 16); }
+PF_INL uint32_t tree_dt(uint32_t p) { return p & 0xffffu; }
+PF_INL uint32_t tree_df(uint32_t p) { return p >> 16; }
+PF_INL uint32_t tree_sat(uint32_t v) { return v < PF_CLIMB_NEAR ? v : PF_CLIMB_NEAR; }
+PF_INL uint32_t tree_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// a value with no gradient (constants, the no-overflow predicates), or with distance m
+PF_INL uint32_t tree_leaf(uint32_t bit, uint32_t m) { return bit ? m << 16 : m; }
+// a compare: x, y are the values the kernel compared (the signed compares': sign-extended, top
+// bit flipped, which keeps their order and so their difference)
+PF_INL uint32_t tree_compare(uint32_t op, const u256& x, const u256& y, uint32_t holds) {
+    if (op == PF_B_EQ) {
+        uint32_t pc = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) pc += (uint32_t)__builtin_popcount(x.l[i] ^ y.l[i]);
+        return tree_pair(pc, holds);
+    }
+    const uint32_t D = PF_CLIMB_NEAR - pf::clz256(climb_absdiff(x, y));
+    return tree_leaf(holds, D ? D : 1u);
+}
+PF_INL uint32_t tree_not(uint32_t p) { return (p >> 16) | (p << 16); }
+PF_INL uint32_t tree_and(uint32_t x, uint32_t y) {
+    return tree_pair(tree_sat(tree_dt(x) + tree_dt(y)), tree_min(tree_df(x), tree_df(y)));
+}
+PF_INL uint32_t tree_or(uint32_t x, uint32_t y) { return tree_not(tree_and(tree_not(x), tree_not(y))); }
+PF_INL uint32_t tree_xor(uint32_t x, uint32_t y) {
+    return tree_pair(tree_min(tree_sat(tree_dt(x) + tree_df(y)), tree_sat(tree_df(x) + tree_dt(y))),
+                     tree_min(tree_sat(tree_dt(x) + tree_dt(y)), tree_sat(tree_df(x) + tree_df(y))));
+}
+PF_INL uint32_t tree_ite(uint32_t c, uint32_t x, uint32_t y) {
+    return tree_pair(tree_min(tree_sat(tree_dt(c) + tree_dt(x)), tree_sat(tree_df(c) + tree_dt(y))),
+                     tree_min(tree_sat(tree_dt(c) + tree_df(x)), tree_sat(tree_df(c) + tree_df(y))));
+}
+// what an assert site whose B value is p adds
+PF_INL uint32_t tree_site(uint32_t p) { return tree_dt(p) ? PF_CLIMB_NEAR - tree_dt(p) : PF_CLIMB_HOLDS; }
 
 
 // Per-unit cycle accounting (profiling builds only, tools/unitprof.py): s_memtime deltas of
@@ -547,6 +592,11 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
     uint32_t Wn[PF_NW_NARROW][8];   // narrow kernels (NREG 8)
     // the 32 bool registers are the bits of one VGPR (bit r = B register r)
     uint32_t Bk = 0u;
+    // tree score only: the registers' distance pairs, a per-lane file indexed by wave-uniform
+    // register numbers; a spilled pair is limb 1 of its slot (.y of its LDS entry)
+    constexpr bool TREE = MODE == MODE_CLIMB_TREE;
+    uint32_t Bd[TREE ? PF_NB : 1];
+#define BPAIR(r) Bd[(r) & 31u]
     // spill slots (lowering under register pressure): dynamically indexed, so the compiler
     // keeps them in private scratch memory, never in the VGPR banks
     // physical spill slot of bytecode slot k
@@ -571,7 +621,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #define PF_DO_ASSERT(v)                                                                       \
     do {                                                                                      \
         root &= (v);                                                                          \
-        if (MODE != MODE_CLIMB && (flags & PF_FLAG_SHORTCIRCUIT) &&                           \
+        if (MODE != MODE_CLIMB && !TREE && (flags & PF_FLAG_SHORTCIRCUIT) &&                  \
             pf::wave_none(pf::wave_mask(root != 0u) & pf::wave_mask(active))) {               \
             In = make_uint4(PF_U_END << 21, 0u, 0u, 0u);                                      \
             sc = 1u;                                                                          \
@@ -587,7 +637,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #define PF_NEXT() continue
 #endif
     uint32_t root = 1u, sc = 0u;
-    uint32_t score = 0u;  // MODE_CLIMB only
+    uint32_t score = 0u;  // MODE_CLIMB, MODE_CLIMB_TREE only
     uint64_t cost = 0;
     // Software-pipelined fetch: the scalar load of instruction i+1 is issued while
     // instruction i executes.  The loop ends at PF_END (pf_batch_create checks that every
@@ -724,6 +774,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 // UMUL_NOOVF's a comes back from LDS, SMOD's signed divisor is rebuilt from |b|
                 if (op == PF_B_UMUL_NOOVF) {
                     BSET(d, pf::iszero256(ub) | (pf::ult256(q, pf::tbl_get(exp_tbl, 64u, 1u)) ^ 1u));
+                    if constexpr (TREE) BPAIR(d) = tree_leaf(BGET(d), PF_CLIMB_NEAR);
                     PF_NEXT();
                 } else if (!sgn) {
                     z = op == PF_W_UDIV ? q : rr;
@@ -768,11 +819,14 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 PF_WAIT_ALL();
                 if (op == PF_B_VAR) {
                     BSET(d, z.l[0]);
+                    if constexpr (TREE) BPAIR(d) = tree_leaf(z.l[0] & 1u, 1u);
                     PF_NEXT();
                 }
                 break;
             case PF_U_CMP: {
                 uint32_t bres;
+                u256 tx, ty;  // tree score: the values compared
+                if constexpr (TREE) { tx = x; ty = y; }
                 switch (op) {
                     case PF_B_EQ: bres = pf::eq256(x, y); break;
                     case PF_B_ULT: bres = pf::ult256(x, y); break;
@@ -783,6 +837,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                         sx.l[7] ^= 0x80000000u;
                         sy.l[7] ^= 0x80000000u;
                         bres = (op == PF_B_SLT) ? pf::ult256(sx, sy) : (pf::ult256(sy, sx) ^ 1u);
+                        if constexpr (TREE) { tx = sx; ty = sy; }
                         break;
                     }
                     default: {  // PF_B_UADD_NOOVF
@@ -798,38 +853,70 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
                 if constexpr (MODE == MODE_CLIMB) {
                     if (I.x & PF_I_ASSERT) score += climb_term(op, x, y, bres);
                 }
+                if constexpr (TREE) {
+                    const uint32_t p = op == PF_B_UADD_NOOVF ? tree_leaf(bres, PF_CLIMB_NEAR)
+                                                             : tree_compare(op, tx, ty, bres);
+                    BPAIR(d) = p;
+                    if (I.x & PF_I_ASSERT) score += tree_site(p);
+                }
                 if (I.x & PF_I_ASSERT) PF_DO_ASSERT(bres);
                 PF_NEXT();
             }
             case PF_U_BOOL:
                 switch (op) {
-                    case PF_B_CONST: BSET(d, aux); break;
-                    case PF_B_AND: BSET(d, BGET(a) & BGET(b)); break;
-                    case PF_B_OR: BSET(d, BGET(a) | BGET(b)); break;
-                    case PF_B_XOR: BSET(d, BGET(a) ^ BGET(b)); break;
-                    case PF_B_NOT: BSET(d, BGET(a) ^ 1u); break;
-                    case PF_B_ITE: BSET(d, BGET(c) ? BGET(a) : BGET(b)); break;
+                    case PF_B_CONST:
+                        BSET(d, aux);
+                        if constexpr (TREE) BPAIR(d) = tree_leaf(aux & 1u, PF_CLIMB_NEAR);
+                        break;
+                    case PF_B_AND:
+                        if constexpr (TREE) BPAIR(d) = tree_and(BPAIR(a), BPAIR(b));
+                        BSET(d, BGET(a) & BGET(b));
+                        break;
+                    case PF_B_OR:
+                        if constexpr (TREE) BPAIR(d) = tree_or(BPAIR(a), BPAIR(b));
+                        BSET(d, BGET(a) | BGET(b));
+                        break;
+                    case PF_B_XOR:
+                        if constexpr (TREE) BPAIR(d) = tree_xor(BPAIR(a), BPAIR(b));
+                        BSET(d, BGET(a) ^ BGET(b));
+                        break;
+                    case PF_B_NOT:
+                        if constexpr (TREE) BPAIR(d) = tree_not(BPAIR(a));
+                        BSET(d, BGET(a) ^ 1u);
+                        break;
+                    case PF_B_ITE:
+                        if constexpr (TREE) BPAIR(d) = tree_ite(BPAIR(c), BPAIR(a), BPAIR(b));
+                        BSET(d, BGET(c) ? BGET(a) : BGET(b));
+                        break;
                     case PF_B_FILL:
                         if (aux & PF_SPILL_LDS) {  // uniform: pf_batch_create's LDS slots
                             BSET(d, exp_tbl[(aux & 3u) * 4u * 64u].x);
+                            if constexpr (TREE) BPAIR(d) = exp_tbl[(aux & 3u) * 4u * 64u].y;
                         } else {
                             BSET(d, spill[PF_SLOT(aux) * 8u]);
+                            if constexpr (TREE) BPAIR(d) = spill[PF_SLOT(aux) * 8u + 1u];
                         }
                         PF_WAIT_ALL();
                         break;
                     case PF_B_SPILL:
-                        if (aux & PF_SPILL_LDS)
-                            exp_tbl[(aux & 3u) * 4u * 64u] = make_uint2(BGET(a), 0u);
-                        else
+                        if (aux & PF_SPILL_LDS) {
+                            exp_tbl[(aux & 3u) * 4u * 64u] = make_uint2(BGET(a), TREE ? BPAIR(a) : 0u);
+                        } else {
                             spill[PF_SLOT(aux) * 8u] = BGET(a);
+                            if constexpr (TREE) spill[PF_SLOT(aux) * 8u + 1u] = BPAIR(a);
+                        }
                         break;
                     default:  // PF_ASSERT
                         if constexpr (MODE == MODE_CLIMB) score += BGET(a) * PF_CLIMB_HOLDS;
+                        if constexpr (TREE) score += tree_site(BPAIR(a));
                         PF_DO_ASSERT(BGET(a));
                         PF_NEXT();
                 }
                 if constexpr (MODE == MODE_CLIMB) {
                     if (I.x & PF_I_ASSERT) score += BGET(d) * PF_CLIMB_HOLDS;
+                }
+                if constexpr (TREE) {
+                    if (I.x & PF_I_ASSERT) score += tree_site(BPAIR(d));
                 }
                 if (I.x & PF_I_ASSERT) PF_DO_ASSERT(BGET(d));
                 PF_NEXT();
@@ -918,8 +1005,9 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 program_end:
     *complete = sc ^ 1u;
     *ops += cost;
-    if constexpr (MODE == MODE_CLIMB) *score_out = score;
+    if constexpr (MODE == MODE_CLIMB || TREE) *score_out = score;
     return root;
+#undef BPAIR
 #undef BGET
 }
 
@@ -1161,7 +1249,7 @@ static_assert(sizeof(pf_climb_set) == 32, "pathfeas.hip copies the states back a
 // evaluates nothing more but still takes items, marking their sets cut: every group of a
 // running set is then either evaluated or accounted for, so the adopt kernel never takes
 // the best of part of a round for the round's best.
-template <int NREG>
+template <int MODE, int NREG>
 PF_INL void climb_body(const pf_set_desc* __restrict__ descs, const uint32_t* __restrict__ order, uint32_t n_sets,
                        const uint4* __restrict__ code, const uint32_t* __restrict__ consts,
                        const uint4* __restrict__ schema, const uint32_t* __restrict__ parents, uint64_t gseed,
@@ -1217,7 +1305,7 @@ PF_INL void climb_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
             const bool active = cand < per_round;
             uint32_t complete = 0, score = 0;
             uint64_t lane_ops = 0;
-            (void)run_program<MODE_CLIMB, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), cand,
+            (void)run_program<MODE, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), cand,
                                                 active, 0u, nullptr, 0u, exp_tbl, &complete, &lane_ops, &prof,
                                                 &score);
             // from round 1 on candidate 0 is the current assignment itself: not a move
@@ -1255,10 +1343,18 @@ PF_INL void climb_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
         deadline_ticks, t0_slot, state, counters, queue
 
 extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_climb_kernel(PF_CLIMB_PARAMS) {
-    climb_body<PF_NW_NARROW + 1>(PF_CLIMB_ARGS);
+    climb_body<MODE_CLIMB, PF_NW_NARROW + 1>(PF_CLIMB_ARGS);
 }
 extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_climb_r16_kernel(PF_CLIMB_PARAMS) {
-    climb_body<16>(PF_CLIMB_ARGS);
+    climb_body<MODE_CLIMB, 16>(PF_CLIMB_ARGS);
+}
+// the tree score's rounds (PF_CLIMB_SCORE_TREE).  A round is a handful of waves on an idle chip,
+// so both take the wide launch bound rather than spill the pair file's operands.
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_climb_tree_kernel(PF_CLIMB_PARAMS) {
+    climb_body<MODE_CLIMB_TREE, PF_NW_NARROW + 1>(PF_CLIMB_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_climb_tree_r16_kernel(PF_CLIMB_PARAMS) {
+    climb_body<MODE_CLIMB_TREE, 16>(PF_CLIMB_ARGS);
 }
 
 // Before a climb's first round, one block per climbed set: the set's working descriptor and

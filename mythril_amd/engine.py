@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .ir import CLIMB_WITNESS, LIMBS, Batch, Program, from_limbs
+from .ir import CLIMB_SCORE_SITES, CLIMB_WITNESS, LIMBS, Batch, Program, climb_score_id, from_limbs
 
 NOT_FOUND = 0xFFFFFFFF
 
@@ -196,12 +196,14 @@ class Engine:
         return res
 
     def climb(self, db, set_ids: Sequence[int], rounds: int, per_round: int, seed: int = 0,
-              timeout_ms: int = 0) -> ClimbResult:
+              timeout_ms: int = 0, score="sites") -> ClimbResult:
         """Climb the given sets (pf_climb_batch; include/pf_bytecode.h, climb contract):
         ``rounds`` scored searches of ``per_round`` candidates, each round's best near miss
         the parent model of the next.  ``db`` is one DeviceBatch, or the list upload_sharded
         returned — ``set_ids`` then index the concatenation of its batches, as check_many's
-        verdicts do, and every set is climbed on the batch that holds it."""
+        verdicts do, and every set is climbed on the batch that holds it.  ``score``: "sites"
+        (pf_climb_batch) or "tree" (pf_climb_batch_scored, the tree score)."""
+        score_id = climb_score_id(score)
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         ids = [int(s) for s in set_ids]
         n = len(ids)
@@ -226,11 +228,14 @@ class Engine:
                 st_, sc_, rd_ = (np.zeros(max(len(mine), 1), dtype=np.uint32) for _ in range(3))
                 vals = np.zeros(max(sum(nv), 1) * LIMBS, dtype=np.uint32)
                 st = _lib.pf_stats()
-                _lib.check(_lib.lib().pf_climb_batch(
-                    d.handle, seed, rounds, per_round, timeout_ms,
-                    _lib.ptr_u32(local) if len(mine) else None, len(mine), _lib.ptr_u32(st_),
-                    _lib.ptr_u32(sc_), _lib.ptr_u32(rd_), _lib.ptr_u32(vals), ctypes.byref(st)),
-                    "pf_climb_batch")
+                tail = (_lib.ptr_u32(local) if len(mine) else None, len(mine), _lib.ptr_u32(st_),
+                        _lib.ptr_u32(sc_), _lib.ptr_u32(rd_), _lib.ptr_u32(vals), ctypes.byref(st))
+                if score_id == CLIMB_SCORE_SITES:
+                    _lib.check(_lib.lib().pf_climb_batch(d.handle, seed, rounds, per_round, timeout_ms, *tail),
+                               "pf_climb_batch")
+                else:
+                    _lib.check(_lib.lib().pf_climb_batch_scored(d.handle, seed, rounds, per_round, score_id,
+                                                                timeout_ms, *tail), "pf_climb_batch_scored")
                 rows, off = vals.reshape(-1, LIMBS), 0
                 for j, i in enumerate(mine):
                     status[i], score[i], rnd[i] = st_[j], sc_[j], rd_[j]

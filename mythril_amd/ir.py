@@ -134,6 +134,22 @@ CLIMB_CUT = 2         # the device deadline cut a round of the set
 CLIMB_HOLDS = 512
 CLIMB_NEAR = 256
 CLIMB_SEED_MUL = 0x9E3779B97F4A7C15
+# pf_climb_score: how a candidate is scored.  "sites" is the score above; "tree" carries two
+# distances (to true, to false) with every B value through NOT / AND / OR / XOR / ITE, so a
+# failing site that is no fused compare still adds CLIMB_NEAR - dt (the header has the table).
+CLIMB_SCORE_SITES = 0
+CLIMB_SCORE_TREE = 1
+CLIMB_SCORES = {"sites": CLIMB_SCORE_SITES, "tree": CLIMB_SCORE_TREE}
+
+
+def climb_score_id(score) -> int:
+    """pf_climb_score of a score's name ("sites", "tree"); an id passes through unchecked (the
+    library refuses the ones it does not know)."""
+    if isinstance(score, str):
+        if score not in CLIMB_SCORES:
+            raise ValueError(f"climb score {score!r}: one of {sorted(CLIMB_SCORES)}")
+        return CLIMB_SCORES[score]
+    return int(score)
 
 
 def climb_round_seed(seed: int, r: int) -> int:

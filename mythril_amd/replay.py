@@ -348,8 +348,13 @@ def main(argv: Optional[List[str]] = None) -> int:
                     help="climb the buckets the search finds nothing for: ROUNDS scored rounds of CANDIDATES "
                          f"candidates (default {gpu_check.CONFIG.climb_candidates}); files answered that way "
                          "report the origin \"climb\"")
+    ap.add_argument("--climb-score", choices=("sites", "tree"), default=None,
+                    help=f"how the climb scores a candidate (default {gpu_check.CONFIG.climb_score}): distances "
+                         "at fused compares only, or carried through the Boolean structure above them")
     args = ap.parse_args(argv)
     cfg = replace(gpu_check.CONFIG, budget=args.budget, timeout_ms=args.timeout_ms)
+    if args.climb_score is not None:
+        cfg = replace(cfg, climb_score=args.climb_score)
     if args.climb is not None:
         cfg = replace(cfg, climb_rounds=args.climb[0],
                       climb_candidates=args.climb[1] if args.climb[1] is not None else cfg.climb_candidates)

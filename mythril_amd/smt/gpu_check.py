@@ -85,6 +85,9 @@ class GpuConfig:
     # where it is on: 16 rounds x 2,048 candidates (profiles/r11_climb.md).
     climb_rounds: int = int(os.environ.get("PF_CLIMB_ROUNDS", "0"))
     climb_candidates: int = int(os.environ.get("PF_CLIMB_CANDIDATES", "2048"))
+    # how the climb scores a candidate (ir.CLIMB_SCORES): "sites", distances at fused compares
+    # only, or "tree", distances carried through NOT / AND / OR / XOR / ITE above the compares
+    climb_score: str = os.environ.get("PF_CLIMB_SCORE", "sites")
 
 
 CONFIG = GpuConfig()
@@ -151,7 +154,10 @@ def _neg_key(key: tuple, cfg: GpuConfig) -> tuple:
     # keeps its negative answers, support_utils.py:59)
     # ... under this configuration: a bucket the climb also left unanswered is negative only
     # for searches that climb the same way
+    # (and scores them the same way: what one score left is not negative for the other)
     climb = (cfg.climb_rounds, cfg.climb_candidates) if cfg.climb_rounds > 0 else (0, 0)
+    if cfg.climb_rounds > 0 and cfg.climb_score != "sites":
+        climb += (cfg.climb_score,)
     return (key, cfg.budget, cfg.seed, cfg.flags, cfg.hints) + climb
 
 
@@ -648,8 +654,9 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                 # the near misses of the buckets the search left: a climb's witness is an
                 # assignment (no candidate index of the search), taken from here on like any
                 # other witness — re-checked on the host, cached, noted
+                how = {} if cfg.climb_score == "sites" else {"score": cfg.climb_score}
                 cl = eng.climb(dbs if len(dbs) > 1 else dbs[0], missed, cfg.climb_rounds,
-                               cfg.climb_candidates, seed=cfg.seed, timeout_ms=climb_ms_left)
+                               cfg.climb_candidates, seed=cfg.seed, timeout_ms=climb_ms_left, **how)
                 timed_out = timed_out or bool(cl.timed_out)
                 n_climb_sat = 0
                 for j, i in enumerate(missed):

@@ -3,6 +3,7 @@
 
     python tools/climb_discharge.py                     # the four-way table at 16 x 2,048
     python tools/climb_discharge.py --climb 24:512
+    python tools/climb_discharge.py --score tree        # the same with the tree score
     python tools/climb_discharge.py --sweep 8:256,16:512,24:512,32:1024,16:2048
     python tools/climb_discharge.py --oracle --scenarios 6 --budget 1024 --climb 4:64
 
@@ -60,11 +61,11 @@ class Recorder:
             if hasattr(self, "_" + name):
                 setattr(self.eng, name, getattr(self, "_" + name))
 
-    def wrap_climb(self, db, set_ids, rounds, per_round, seed=0, timeout_ms=0):
+    def wrap_climb(self, db, set_ids, rounds, per_round, seed=0, timeout_ms=0, **how):
         from mythril_amd import ir
 
         t = time.perf_counter()
-        r = self._climb(db, set_ids, rounds, per_round, seed=seed, timeout_ms=timeout_ms)
+        r = self._climb(db, set_ids, rounds, per_round, seed=seed, timeout_ms=timeout_ms, **how)
         self.climb_wall += time.perf_counter() - t
         self.climb_ms += r.kernel_ms
         for s, rd in zip(r.status, r.round):
@@ -116,6 +117,7 @@ def run_config(c, unsat, cfg, eng):
     answered = sum(m is not None for m in models)
     return {
         "hints": cfg.hints, "climb": [cfg.climb_rounds, cfg.climb_candidates] if cfg.climb_rounds else None,
+        "score": cfg.climb_score if cfg.climb_rounds else None,
         "queries": n, "answered": answered, "pct": round(100.0 * answered / max(n, 1), 2),
         "buckets_searched": buckets, "buckets_answered": sum(origins.values()),
         "bucket_origin": origins, "climbed": climbed, "climb_sat": climb_sat,
@@ -139,6 +141,8 @@ def main(argv=None) -> int:
                     help="default: the recommended 16 rounds of GpuConfig.climb_candidates (2,048)")
     ap.add_argument("--sweep", default=None, metavar="R:N,R:N,...",
                     help="hints off only: climb off, then each pair")
+    ap.add_argument("--score", choices=("sites", "tree"), default="sites",
+                    help="how the climb scores a candidate (GpuConfig.climb_score)")
     ap.add_argument("--oracle", action="store_true", help="the tests' oracle-backed engine instead of the GPU")
     args = ap.parse_args(argv)
 
@@ -150,17 +154,17 @@ def main(argv=None) -> int:
         import pyoracle as O
         from mythril_amd import keccak_manager as KM
         from mythril_amd.smt import symbol_factory
-        from climb_model import ClimbOracleEngine
+        from climb_tree_model import TreeOracleEngine
 
         KM.KeccakFunctionManager.find_concrete_keccak = staticmethod(
             lambda data: symbol_factory.BitVecVal(
                 int.from_bytes(O.keccak256(data.value.to_bytes(data.size() // 8, "big")), "big"), 256))
-        eng = ClimbOracleEngine()
+        eng = TreeOracleEngine()
         E.get_engine = lambda device=None: eng
         gpu_check.CONFIG.workers = 1
     else:
         eng = E.get_engine()
-    base = replace(gpu_check.CONFIG, climb_rounds=0)
+    base = replace(gpu_check.CONFIG, climb_rounds=0, climb_score=args.score)
     if args.budget:
         base = replace(base, budget=args.budget)
     c = corpus.build(args.scenarios, 2, seed=2024)
@@ -176,6 +180,8 @@ def main(argv=None) -> int:
     for cfg in configs:
         rows.append(run_config(c, unsat, cfg, eng))
         print(json.dumps(rows[-1], sort_keys=True), flush=True)
+    print()
+    print(f"score: {args.score}")
     print()
     print("| hints | climb | queries answered | % | buckets answered / searched | climbed | climb witnesses | "
           "witness rounds | climb kernel / wall ms per climbed bucket | search kernel / wall ms per bucket | "

@@ -151,6 +151,32 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
                           uint32_t* status_out, uint32_t* score_out, uint32_t* round_out,
                           uint32_t* values_out, pf_stats* stats);
 
+/* counts_out[i] = the assert sites of set set_ids[i]'s device program (include/pf_bytecode.h,
+ * census contract): the row length of pf_census_batch, PF_CLIMB_HOLDS x it the score of a
+ * climb's witness.  No device work.  A set id out of range: error.                          */
+int pf_batch_site_counts(uint64_t handle, const uint32_t* set_ids, size_t n, uint32_t* counts_out);
+/* Census of the sets set_ids[0 .. n) over candidates [0, budget) under global_seed — the plain
+ * search's candidates (include/pf_bytecode.h, census contract): which assert sites hold how
+ * often, and how near the nearest candidate came.  holds_out, alive_out, sole_out: n_sites(set)
+ * u32 per request, concatenated in request order; best_fails_out, best_cand_out, status_out:
+ * one u32 per request (PF_CENSUS_DONE / PF_CENSUS_CUT).  Any output may be NULL.  stats:
+ * evals_full = cands_decided = candidate evaluations, n_sat = sets whose best_fails is 0,
+ * kernel_ms and timed_out as for pf_climb_batch.  Every launch is enqueued on the batch's
+ * stream before the one synchronisation that reads the results back.  budget == 0, a set id out
+ * of range or repeated, or a set of more than PF_CENSUS_MAX_SITES sites: error, nothing
+ * launched.  Nothing the search or the climb reads is changed by it.                        */
+int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint32_t timeout_ms,
+                    const uint32_t* set_ids, size_t n, uint32_t* holds_out, uint32_t* alive_out,
+                    uint32_t* sole_out, uint32_t* best_fails_out, uint32_t* best_cand_out,
+                    uint32_t* status_out, pf_stats* stats);
+/* Host only, like pf_device_batch (same fold gate, PF_DEVICE_FOLD read per call): for every
+ * assert site of every set's device program, in set and site order, the ordinal — among the
+ * PF_ASSERTs of the set's lowered program, from 0 — of the PF_ASSERT it stands for.  The fold
+ * pass deletes the asserts it proves true, so those ordinals are absent.  site_assert_out: room
+ * for n_ins entries; n_out[s] = the sites of set s.                                          */
+int pf_device_sites(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
+                    const pf_set_desc* descs, size_t n_sets, uint32_t* site_assert_out, uint32_t* n_out);
+
 /* Evaluate set `set` on n_cand explicit assignments, SoA limbs [var][limb][cand].          */
 int pf_eval_assignments(uint64_t handle, uint32_t set, const uint32_t* soa, uint32_t n_cand,
                         uint8_t* sat_out);

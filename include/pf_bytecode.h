@@ -369,6 +369,35 @@ enum pf_climb_score {
     PF_CLIMB_SCORE_TREE = 1
 };
 
+/* ---- census contract ------------------------------------------------------------ */
+/* A census (pf_census_batch) says what blocks a set: it counts, at every assert site, over the
+ * plain search's own candidates.  It is defined on the set's device program (what
+ * pf_batch_create uploads and pf_device_batch returns).  The sites of a set are, in program
+ * order, every PF_ASSERT and every B op carrying PF_I_ASSERT — n_sites, the number the climb
+ * contract's witness score counts (pf_batch_site_counts).
+ *
+ * Candidates [0, budget) are generated under global seed G with the batch's own parents, exactly
+ * as pf_check_batch generates them.  Every candidate runs the whole program: nothing
+ * short-circuits.  Per set, all u32:
+ *    holds[j]   candidates at which site j's value is true
+ *    alive[j]   candidates at which sites 0 .. j all hold; alive[n_sites - 1] is the number of
+ *               witnesses among the candidates
+ *    sole[j]    candidates with exactly one failing site, that site being j
+ *    best_fails, best_cand
+ *               the fewest failing sites of any candidate and the smallest candidate index that
+ *               has so few; best_fails == 0 exactly when pf_check_batch finds a witness under
+ *               (G, budget), and best_cand is then its found[s]
+ *    status     PF_CENSUS_DONE, or PF_CENSUS_CUT: the device deadline kept some 64-candidate
+ *               group of the set from being evaluated.  A cut set reports 0 in every count and
+ *               0xFFFFFFFF for best_fails and best_cand (nothing is known)
+ * A set without a site (a program folded to a bare PF_END) has empty rows, best_fails = 0 and
+ * best_cand = 0.  A census takes sets of at most PF_CENSUS_MAX_SITES sites.                 */
+enum pf_census_status {
+    PF_CENSUS_DONE = 0,
+    PF_CENSUS_CUT = 1
+};
+#define PF_CENSUS_MAX_SITES 0xffffu
+
 /* flags for pf_check_batch */
 #define PF_FLAG_SHORTCIRCUIT 1u  /* stop a wave's set evaluation once all its lanes are false */
 #define PF_FLAG_EARLY_EXIT 2u    /* stop a set once any candidate satisfies it             */

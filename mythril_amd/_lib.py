@@ -70,6 +70,11 @@ SIGNATURES = {
     "pf_climb_batch_scored": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_uint32, ctypes.c_uint32, _u32p, _sz, _u32p, _u32p, _u32p,
                                              _u32p, ctypes.POINTER(pf_stats)]),
+    "pf_batch_site_counts": (ctypes.c_int, [ctypes.c_uint64, _u32p, _sz, _u32p]),
+    "pf_census_batch": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                       _u32p, _sz, _u32p, _u32p, _u32p, _u32p, _u32p, _u32p,
+                                       ctypes.POINTER(pf_stats)]),
+    "pf_device_sites": (ctypes.c_int, [_u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p, _u32p]),
     "pf_eval_assignments": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, _u32p,
                                            ctypes.c_uint32, _u8p]),
     "pf_eval_program": (ctypes.c_int, [ctypes.c_int, _u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p,
@@ -221,3 +226,22 @@ def device_batch(code, consts, descs):
                             ptr_u32(descs), len(descs), ptr_u32(out), ctypes.byref(n), ptr_u32(dout),
                             ptr_u32(pool), cap, ctypes.byref(nc)), "pf_device_batch")
     return out[:n.value], dout, pool[:nc.value]
+
+
+def device_sites(code, consts, descs):
+    """pf_device_sites (host only): per set, for every assert site of the device program
+    pf_batch_create would upload, the ordinal of the lowered program's PF_ASSERT it stands for
+    (a list of uint32 arrays, one per set)."""
+    L = lib()
+    code = np.ascontiguousarray(code, dtype=np.uint32)
+    descs = np.ascontiguousarray(descs, dtype=np.uint32)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    out = np.zeros(max(len(code), 1), dtype=np.uint32)
+    cnt = np.zeros(max(len(descs), 1), dtype=np.uint32)
+    check(L.pf_device_sites(ptr_u32(code), len(code), ptr_u32(consts) if consts.size else None, len(consts),
+                            ptr_u32(descs), len(descs), ptr_u32(out), ptr_u32(cnt)), "pf_device_sites")
+    res, off = [], 0
+    for k in cnt[:len(descs)].tolist():
+        res.append(out[off:off + k].copy())
+        off += k
+    return res

@@ -141,9 +141,15 @@ struct Batch {
     std::vector<uint32_t> h_sites;
     void* c_mem = nullptr;
     size_t c_cap = 0;
+    // census (pf_census_batch): the census block — per-set states, the rows holds / alive / sole
+    // of every set, this call's tables — is allocated by the batch's first census and lives as
+    // long as the batch
+    void* s_mem = nullptr;
+    size_t s_cap = 0;
     ~Batch() {  // the device block goes back to its device's pool first (release_batch)
         if (d_mem) hipFree(d_mem);
         if (c_mem) hipFree(c_mem);
+        if (s_mem) hipFree(s_mem);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
     }
@@ -209,6 +215,10 @@ void release_batch(Dev* D, Batch* B) {
     if (D && B->c_mem) {
         pool_release(D, B->c_mem, B->c_cap);
         B->c_mem = nullptr;
+    }
+    if (D && B->s_mem) {
+        pool_release(D, B->s_mem, B->s_cap);
+        B->s_mem = nullptr;
     }
     if (D) {
         std::lock_guard<std::mutex> pk(g_pool_mu);
@@ -438,7 +448,7 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
 
 extern "C" {
 
-int pf_version(void) { return 3; }
+int pf_version(void) { return 4; }
 
 // Host only (no HIP call, tests/test_device_program.py): the program pf_batch_create would put
 // on the device — traffic / unit bits recomputed from the opcodes, then the fold pass (whatever
@@ -481,6 +491,20 @@ int pf_device_batch(const uint32_t* code, size_t n_ins, const uint32_t* consts, 
     *n_ins_out = out.size() / 4;
     memcpy(descs_out, d.data(), n_sets * sizeof(pf_set_desc));
     if (np && pc) memcpy(consts_out, pc, np * 32);
+    return 0;
+}
+
+// Host only: the PF_ASSERT of the lowered program behind every assert site of the device programs
+// pf_batch_create would upload for this batch (pf_devprog.h device_sites: pf_device_batch's gate,
+// PF_DEVICE_FOLD read on every call).
+int pf_device_sites(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
+                    const pf_set_desc* descs, size_t n_sets, uint32_t* site_assert_out, uint32_t* n_out) {
+    const SiteMap M = device_sites(code, n_ins, consts, n_const, descs, n_sets, device_fold_env());
+    if (M.asserts.size() > n_ins || M.cnt.size() != n_sets)
+        return set_err(errorf("pf_device_sites: %zu sites of %zu sets for %zu instructions", M.asserts.size(),
+                              M.cnt.size(), n_ins));
+    if (!M.asserts.empty()) memcpy(site_assert_out, M.asserts.data(), M.asserts.size() * 4);
+    if (n_sets) memcpy(n_out, M.cnt.data(), n_sets * 4);
     return 0;
 }
 
@@ -1068,6 +1092,166 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
         const size_t nv = B->h_descs[s].n_vars;
         if (values_out && nv) memcpy(values_out + off * 8, hv + (size_t)wvoff[s] * 8, nv * 32);
         off += nv;
+    }
+    if (stats) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+        stats->evals_full = h[0];
+        stats->cands_decided = h[1];
+        stats->n_sat = n_sat;
+        stats->kernel_ms = ms;
+        stats->timed_out = h[3] ? 1u : 0u;
+    }
+    return 0;
+}
+
+int pf_batch_site_counts(uint64_t handle, const uint32_t* set_ids, size_t n, uint32_t* counts_out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    if (!B) return fail("pf_batch_site_counts: null batch");
+    if (n && (!set_ids || !counts_out)) return fail("pf_batch_site_counts: null argument");
+    for (size_t i = 0; i < n; i++) {
+        if (set_ids[i] >= B->n_sets)
+            return fail("pf_batch_site_counts: set %u out of range (%zu sets)", set_ids[i], B->n_sets);
+        counts_out[i] = B->h_sites[set_ids[i]];
+    }
+    return 0;
+}
+
+int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint32_t timeout_ms,
+                    const uint32_t* set_ids, size_t n, uint32_t* holds_out, uint32_t* alive_out,
+                    uint32_t* sole_out, uint32_t* best_fails_out, uint32_t* best_cand_out,
+                    uint32_t* status_out, pf_stats* stats) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    if (!B) return fail("pf_census_batch: null batch");
+    if (budget == 0) return fail("pf_census_batch: budget must be at least 1");
+    if (n && !set_ids) return fail("pf_census_batch: null set_ids");
+    const size_t ns = B->n_sets;
+    {
+        std::vector<uint8_t> seen(ns, 0);
+        for (size_t i = 0; i < n; i++) {
+            if (set_ids[i] >= ns) return fail("pf_census_batch: set %u out of range (%zu sets)", set_ids[i], ns);
+            if (seen[set_ids[i]]) return fail("pf_census_batch: set %u requested twice", set_ids[i]);
+            if (B->h_sites[set_ids[i]] > PF_CENSUS_MAX_SITES)
+                return fail("pf_census_batch: set %u has %u sites (at most %u)", set_ids[i], B->h_sites[set_ids[i]],
+                            PF_CENSUS_MAX_SITES);
+            seen[set_ids[i]] = 1;
+        }
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0) return 0;
+    const uint32_t groups = (uint32_t)(((uint64_t)budget + 63u) / 64u);
+    if ((uint64_t)n * groups > 0xffffffffull) return fail("pf_census_batch: %zu sets x %u groups is too many items", n, groups);
+    Dev* D = use_dev(B->device);
+    if (!D) return -1;
+    hipStream_t st = D->stream;
+    if (switch_stream(D, st)) return -1;
+
+    // the census block: [states | rows: per set holds, alive, sole | per set: first row, sites |
+    // this call's set ids, 8-register sets first].  Its size depends on the batch alone.
+    std::vector<uint32_t> row_off(ns);
+    uint64_t n_rows = 0;
+    for (size_t s = 0; s < ns; s++) {
+        row_off[s] = (uint32_t)n_rows;
+        n_rows += 3ull * B->h_sites[s];
+    }
+    if (n_rows + ns > 0xffffffffull) return fail("pf_census_batch: %llu row entries", (unsigned long long)n_rows);
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t o_st = 0, o_rows = o_st + al(ns * sizeof(pf_census_set)), o_tab = o_rows + al((size_t)n_rows * 4 + 4),
+                 total = o_tab + al(3 * ns * 4);
+    if (!B->s_mem) {
+        B->s_mem = pool_acquire(D, total, &B->s_cap);
+        if (!B->s_mem) return fail("pf_census_batch: hipMalloc(%zu) failed", total);
+    }
+    uint8_t* sb = static_cast<uint8_t*>(B->s_mem);
+    pf_census_set* d_state = reinterpret_cast<pf_census_set*>(sb + o_st);
+    uint32_t* d_rows = reinterpret_cast<uint32_t*>(sb + o_rows);
+    uint32_t* d_rowoff = reinterpret_cast<uint32_t*>(sb + o_tab);
+    uint32_t *d_nsites = d_rowoff + ns, *d_req = d_nsites + ns;
+
+    // this call's sets in launch order: the 8-register ones, then the 16-register ones
+    std::vector<uint32_t> req;
+    req.reserve(n);
+    for (int part = 0; part < 2; ++part)
+        for (size_t i = 0; i < n; i++)
+            if ((int)B->h_wide[set_ids[i]] == part) req.push_back(set_ids[i]);
+    const size_t n_narrow = (size_t)std::count_if(req.begin(), req.end(), [&](uint32_t s) { return !B->h_wide[s]; });
+
+    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
+    const size_t in_bytes = 3 * ns * 4, out_bytes = cbytes + ns * sizeof(pf_census_set) + (size_t)n_rows * 4;
+    uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
+    if (!pin) return fail("pf_census_batch: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
+    memcpy(pin, row_off.data(), ns * 4);
+    memcpy(pin + ns * 4, B->h_sites.data(), ns * 4);
+    memset(pin + 2 * ns * 4, 0, ns * 4);
+    memcpy(pin + 2 * ns * 4, req.data(), n * 4);
+    HIPCHK(hipMemcpyAsync(d_rowoff, pin, in_bytes, hipMemcpyHostToDevice, st));
+
+    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
+    uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
+    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
+    // the launches, back to back on the stream: the scratch reset (found[] is left alone), the
+    // census block's reset, the two parts' census launches; nothing here waits for the device
+    hipLaunchKernelGGL(pf_reset_kernel, dim3((PF_SCRATCH_BYTES / 4 + 255u) / 256u), dim3(256), 0, st, B->d_scratch,
+                       (uint32_t)(PF_SCRATCH_BYTES / 4), B->d_found, 0u);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B->ev0, st));
+    {
+        const uint64_t cells = n_rows + ns;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((cells + 255u) / 256u, 1024u);
+        hipLaunchKernelGGL(pf_census_init_kernel, dim3(blocks), dim3(256), 0, st, d_rowoff, d_nsites, (uint32_t)ns,
+                           d_state, d_rows, (uint32_t)n_rows);
+        HIPCHK(hipGetLastError());
+    }
+    const uint64_t deadline = timeout_ms ? (uint64_t)timeout_ms * 100000ull : 0ull;  // 100 MHz
+    for (int part = 0; part < 2; ++part) {
+        const size_t first = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
+        if (np == 0) continue;
+        const uint64_t items = (uint64_t)np * groups;
+        const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early);
+        const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
+        hipLaunchKernelGGL(part == 0 ? pf_census_kernel : pf_census_r16_kernel, dim3(blocks),
+                           dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, d_req + first, (uint32_t)np, B->d_code,
+                           B->d_consts, B->d_schema, B->d_parents, global_seed, budget, groups, deadline, d_t0,
+                           d_state, d_rows, d_counters, d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(B->ev1, st));
+    // counters, states and rows in the staging buffer; the stream orders these copies after the
+    // upload above has been consumed
+    HIPCHK(hipMemcpyAsync(pin, B->d_scratch + PF_COUNTER_OFF / 4, cbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin + cbytes, d_state, ns * sizeof(pf_census_set), hipMemcpyDeviceToHost, st));
+    if (n_rows)
+        HIPCHK(hipMemcpyAsync(pin + cbytes + ns * sizeof(pf_census_set), d_rows, (size_t)n_rows * 4,
+                              hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const unsigned long long* hs = reinterpret_cast<const unsigned long long*>(pin);
+    const pf_census_set* hst = reinterpret_cast<const pf_census_set*>(pin + cbytes);
+    const uint32_t* hr = reinterpret_cast<const uint32_t*>(pin + cbytes + ns * sizeof(pf_census_set));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
+        for (int k = 0; k < 4; k++) h[k] += hs[i * 16 + k];
+    uint64_t n_sat = 0;
+    size_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t s = set_ids[i];
+        const size_t k = B->h_sites[s];
+        const bool is_cut = hst[s].cut != 0u;
+        const uint32_t* r = hr + row_off[s];
+        uint32_t* outs[3] = {holds_out, alive_out, sole_out};
+        for (int a = 0; a < 3; a++) {
+            if (!outs[a] || !k) continue;
+            if (is_cut) memset(outs[a] + off, 0, k * 4);
+            else memcpy(outs[a] + off, r + (size_t)a * k, k * 4);
+        }
+        off += k;
+        const uint32_t bf = is_cut ? 0xffffffffu : (uint32_t)(hst[s].best >> 32);
+        const uint32_t bc = is_cut ? 0xffffffffu : (uint32_t)hst[s].best;
+        if (best_fails_out) best_fails_out[i] = bf;
+        if (best_cand_out) best_cand_out[i] = bc;
+        if (status_out) status_out[i] = is_cut ? PF_CENSUS_CUT : PF_CENSUS_DONE;
+        n_sat += bf == 0u;
     }
     if (stats) {
         float ms = 0.f;

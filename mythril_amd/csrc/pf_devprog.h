@@ -162,7 +162,39 @@ struct Work {
         std::vector<uint32_t> readers;
     };
     Pending pend[PF_NW + 1];
+    // site bookkeeping (SiteMap below), filled only while one is collected: origin[k] = the
+    // PF_ASSERT that fuse_asserts moved onto instruction k
+    std::vector<int64_t> origin;
 };
+
+// Which PF_ASSERT of the lowered program every assert site of the device program stands for
+// (pf_device_sites): asserts holds, per site and in set and site order, the assert's ordinal
+// among the set's PF_ASSERTs; cnt[s] = the sites of set s.  The working copy keeps every
+// instruction at its lowered index until append_kept, so an assert is followed by its index:
+// the fold pass drops the ones it proves true, fuse_asserts moves one onto the last writer of
+// its B register (at most one per writer).
+struct SiteMap {
+    std::vector<uint32_t> asserts, cnt;
+};
+static inline void collect_sites(const Work& T, SiteMap& M) {
+    std::vector<uint32_t> ord(T.n, 0);
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < T.n; i++)
+        if (pf_ins_op(T.P[4 * (size_t)i]) == PF_ASSERT) ord[i] = k++;
+    uint32_t sites = 0;
+    for (uint32_t i = 0; i < T.n; i++) {
+        if (T.drop[i]) continue;
+        const uint32_t w0 = T.P[4 * (size_t)i];
+        if (pf_ins_op(w0) == PF_ASSERT) {
+            M.asserts.push_back(ord[i]);
+            sites++;
+        } else if ((w0 & PF_I_ASSERT) && T.origin[i] >= 0) {
+            M.asserts.push_back(ord[(size_t)T.origin[i]]);
+            sites++;
+        }
+    }
+    M.cnt.push_back(sites);
+}
 
 // Constants of the device programs' own (pf_fold.h: a constant result that is neither 0 nor in
 // the set's pool): vals holds 8 u32 each in set order, cnt[s] how many set s has.  Their indices
@@ -208,6 +240,7 @@ static inline void fuse_asserts(Work& T) {
                 if ((unit == PF_U_CMP || unit == PF_U_BOOL) && !(P[4 * (size_t)k] & PF_I_ASSERT)) {
                     P[4 * (size_t)k] |= PF_I_ASSERT;
                     T.drop[i] = 1;
+                    if (!T.origin.empty()) T.origin[(size_t)k] = i;
                 }
             }
         } else if (PF_OP_WRITES_B(op)) {
@@ -461,13 +494,14 @@ static inline void append_kept(const Work& T, std::vector<uint32_t>& code_out, p
 // result is read against the caller's pool) collects the sets' own constants.
 static inline void device_program_range(const uint32_t* code_fixed, std::vector<pf_set_desc>& descs_out, size_t s0,
                                  size_t s1, std::vector<uint32_t>& code_out, const uint32_t* consts,
-                                 size_t n_const, int fold, OwnConsts* own = nullptr) {
+                                 size_t n_const, int fold, OwnConsts* own = nullptr, SiteMap* sites = nullptr) {
     Work T;
     for (size_t s = s0; s < s1; s++) {
         pf_set_desc& d = descs_out[s];
         T.n = d.n_ins;
         T.P.assign(code_fixed + 4 * (size_t)d.code_off, code_fixed + 4 * ((size_t)d.code_off + T.n));
         T.drop.assign(T.n, 0);
+        if (sites) T.origin.assign(T.n, -1);
         if (fold) fold_constants(T, s, d, consts, n_const, own);
         if (fold != 2) {
             fuse_asserts(T);
@@ -476,6 +510,7 @@ static inline void device_program_range(const uint32_t* code_fixed, std::vector<
             lds_spill_slots(T);
             forward_results(T);
         }
+        if (sites) collect_sites(T, *sites);
         append_kept(T, code_out, d);
     }
 }
@@ -526,7 +561,9 @@ static void run_ranges(size_t n, F&& fn) {
 // keeps its range.
 static inline void device_program(const uint32_t* code_fixed, size_t n_fixed, std::vector<pf_set_desc>& descs_out,
                            const std::vector<size_t>& cut, std::vector<uint32_t>& code_out, const uint32_t* consts,
-                           size_t n_const, int fold, std::vector<uint32_t>* pool_out = nullptr) {
+                           size_t n_const, int fold, std::vector<uint32_t>* pool_out = nullptr,
+                           SiteMap* sites = nullptr) {
+    // (a site map is collected by the serial pass only: its caller passes the one range {0, n_sets})
     const size_t nt = cut.size() - 1, n_sets = descs_out.size();
     code_out.clear();
     const bool owning = pool_out && fold;
@@ -535,7 +572,7 @@ static inline void device_program(const uint32_t* code_fixed, size_t n_fixed, st
     if (nt == 1) {
         code_out.reserve(n_fixed);
         device_program_range(code_fixed, descs_out, 0, n_sets, code_out, consts, n_const, fold,
-                             owning ? &own[0] : nullptr);
+                             owning ? &own[0] : nullptr, sites);
     } else {
         std::vector<std::vector<uint32_t>> outs(nt);
         run_ranges(nt, [&](size_t t) {
@@ -571,6 +608,20 @@ static inline void device_program(const uint32_t* code_fixed, size_t n_fixed, st
             d.const_off = at;
         }
     }
+}
+
+// The site map of the batch pf_batch_create would upload (pf_device_sites): the same passes under
+// the same gate — fold (the PF_DEVICE_FOLD value) only for batches of PF_FOLD_MIN_SETS sets or
+// more, the sets' own constants collected as the upload collects them — on one thread.
+static inline SiteMap device_sites(const uint32_t* code, size_t n_ins, const uint32_t* consts, size_t n_const,
+                                   const pf_set_desc* descs, size_t n_sets, int fold) {
+    const std::vector<uint32_t> fixed = stamped(code, n_ins);
+    std::vector<pf_set_desc> d(descs, descs + n_sets);
+    std::vector<uint32_t> out, pool;
+    SiteMap M;
+    device_program(fixed.data(), fixed.size(), d, std::vector<size_t>{0, n_sets}, out, consts, n_const,
+                   n_sets >= PF_FOLD_MIN_SETS ? fold : 0, &pool, &M);
+    return M;
 }
 
 // What prepare_program hands the upload: the device programs, their descriptors, the device

@@ -482,7 +482,17 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
 // assert sites (include/pf_bytecode.h, climb contract)
 // MODE_CLIMB_TREE: MODE_CLIMB with the tree score (PF_CLIMB_SCORE_TREE): every B register carries
 // its two distances beside its bit, and a failing site adds PF_CLIMB_NEAR - dt
-enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2, MODE_CLIMB_TREE = 3 };
+// MODE_CENSUS: MODE_GEN's candidates, no short-circuit, and the wave's counts taken at the assert
+// sites (include/pf_bytecode.h, census contract)
+enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2, MODE_CLIMB_TREE = 3, MODE_CENSUS = 4 };
+
+// Where a census wave's per-site counts go: the set's holds[] and alive[] rows (n_sites u32
+// each, in the batch's census block).
+struct CensusRows {
+    uint32_t* holds;
+    uint32_t* alive;
+    uint32_t n_sites;
+};
 
 // |a - b| of two 256-bit values taken as unsigned
 PF_INL u256 climb_absdiff(const u256& x, const u256& y) {
@@ -584,7 +594,7 @@ template <int MODE, int NREG>
 PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_t flags,
                             const uint32_t* __restrict__ soa, uint32_t soa_n,
                             uint2* exp_tbl, uint32_t* complete, uint64_t* ops, UnitProf* prof,
-                            uint32_t* score_out = nullptr) {
+                            uint32_t* score_out = nullptr, const CensusRows* cen = nullptr) {
     // No initialisation: pf_batch_create rejects programs that read a register before
     // writing it, so the banks never leak values between candidates.
     constexpr int LPB = 16 / NREG;  // limbs per vector
@@ -620,6 +630,21 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
     // instruction becomes END; the fetch in flight is dropped)
 #define PF_DO_ASSERT(v)                                                                       \
     do {                                                                                      \
+        if constexpr (MODE == MODE_CENSUS) {                                                  \
+            /* holds[site] += lanes where the site holds, alive[site] += lanes where every */ \
+            /* site so far holds: two ballots' popcounts, posted by lane 0 as atomics that */ \
+            /* return nothing (skipped when 0).  site is wave-uniform: the stream is.      */ \
+            const uint32_t h_ = (uint32_t)__popcll(pf::wave_mask(active && (v) != 0u));       \
+            root &= (v);                                                                      \
+            const uint32_t a_ = (uint32_t)__popcll(pf::wave_mask(active && root != 0u));      \
+            fails = (v) ? fails : (((fails & 0xffff0000u) + 0x10000u) | site);                \
+            if ((threadIdx.x & 63u) == 0u && site < cen->n_sites) {                           \
+                if (h_) atomicAdd(cen->holds + site, h_);                                     \
+                if (a_) atomicAdd(cen->alive + site, a_);                                     \
+            }                                                                                 \
+            site++;                                                                           \
+            break;                                                                            \
+        }                                                                                     \
         root &= (v);                                                                          \
         if (MODE != MODE_CLIMB && !TREE && (flags & PF_FLAG_SHORTCIRCUIT) &&                  \
             pf::wave_none(pf::wave_mask(root != 0u) & pf::wave_mask(active))) {               \
@@ -638,6 +663,9 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
 #endif
     uint32_t root = 1u, sc = 0u;
     uint32_t score = 0u;  // MODE_CLIMB, MODE_CLIMB_TREE only
+    // MODE_CENSUS only: the ordinal of the next assert site (wave-uniform), and the lane's failing
+    // sites so far — their count in the high half, the last one's ordinal in the low half
+    uint32_t site = 0u, fails = 0u;
     uint64_t cost = 0;
     // Software-pipelined fetch: the scalar load of instruction i+1 is issued while
     // instruction i executes.  The loop ends at PF_END (pf_batch_create checks that every
@@ -1006,6 +1034,8 @@ program_end:
     *complete = sc ^ 1u;
     *ops += cost;
     if constexpr (MODE == MODE_CLIMB || TREE) *score_out = score;
+    if constexpr (MODE == MODE_CENSUS) *score_out = fails;
+    (void)site;
     return root;
 #undef BPAIR
 #undef BGET
@@ -1452,6 +1482,150 @@ pf_climb_adopt_kernel(const pf_set_desc* __restrict__ descs, const pf_set_desc* 
     }
     if (blockIdx.x == 0u)
         for (uint32_t i = threadIdx.x; i < n_queue; i += blockDim.x) queue[i] = 0u;
+}
+
+// ---- census: what blocks a set (include/pf_bytecode.h, census contract) -----------------
+// Per-set state of a census, in the batch's census block (pathfeas.hip).  `best` takes the waves'
+// 64-bit atomicMin of (failing sites << 32) | candidate: the fewest failing sites, ties to the
+// smallest index; ~0 = nothing posted.  The set's rows are rows[row_off ..): holds[n_sites],
+// alive[n_sites], sole[n_sites].
+struct pf_census_set {
+    unsigned long long best;
+    uint32_t row_off;
+    uint32_t n_sites;
+    uint32_t cut;  // the deadline left a group of this set unevaluated
+    uint32_t pad[3];
+};
+static_assert(sizeof(pf_census_set) == 32, "pathfeas.hip copies the states back as 8 u32 each");
+
+// At the start of a census call: the rows zeroed, every set's state reset over its row range.
+extern "C" __global__ void __launch_bounds__(256)
+pf_census_init_kernel(const uint32_t* __restrict__ row_off, const uint32_t* __restrict__ n_sites, uint32_t n_sets,
+                      pf_census_set* __restrict__ state, uint32_t* __restrict__ rows, uint32_t n_rows) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rows + n_sets; i += stride) {
+        if (i < n_rows) {
+            rows[i] = 0u;
+        } else {
+            const uint32_t s = i - n_rows;
+            pf_census_set z;
+            z.best = ~0ull;
+            z.row_off = row_off[s];
+            z.n_sites = n_sites[s];
+            z.cut = 0u;
+            z.pad[0] = z.pad[1] = z.pad[2] = 0u;
+            state[s] = z;
+        }
+    }
+}
+
+// Items (set, 64-candidate group) from the search's work queue, as a climb round takes them.  A
+// wave runs its group in census mode — holds[] and alive[] are counted inside run_program, one
+// atomic per site, row and group — then attributes sole[] (the lanes with exactly one failing
+// site add 1 at that site) and posts the group's fewest-failing candidate with one atomicMin.
+// Past the deadline a wave evaluates nothing more but still takes items, marking their sets cut,
+// so a set's counts are either over every group or discarded by the host.
+template <int NREG>
+PF_INL void census_body(const pf_set_desc* __restrict__ descs, const uint32_t* __restrict__ order, uint32_t n_sets,
+                        const uint4* __restrict__ code, const uint32_t* __restrict__ consts,
+                        const uint4* __restrict__ schema, const uint32_t* __restrict__ parents, uint64_t gseed,
+                        uint32_t budget, uint32_t groups, uint64_t deadline_ticks, uint64_t* __restrict__ t0_slot,
+                        pf_census_set* __restrict__ state, uint32_t* __restrict__ rows,
+                        unsigned long long* __restrict__ counters, uint32_t* __restrict__ queue) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const uint32_t n_items = n_sets * groups;
+    __shared__ uint2 pf_exp_lds[PF_SEARCH_LDS_U2];
+    uint2* exp_tbl = exp_tbl_of(pf_exp_lds);
+
+    uint64_t t0 = 0;
+    if (deadline_ticks) {  // the first wave of the call's first launch stamps the start (check_body)
+        uint64_t now = __builtin_amdgcn_s_memrealtime();
+        uint64_t prev = __hip_atomic_load(t0_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prev == 0) prev = atomicCAS((unsigned long long*)t0_slot, 0ull, (unsigned long long)now);
+        const uint64_t t = prev ? prev : now;
+        t0 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)t) |
+             ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(t >> 32)) << 32);
+    }
+    UnitProf prof;
+#pragma unroll
+    for (int i = 0; i < PF_PROF_BUCKETS; i++) prof.c[i] = 0;
+    uint64_t decided = 0;
+    uint32_t cut = 0u;
+    for (uint32_t qi = 0; qi < PF_EARLY_QUEUES; ++qi) {
+        const uint32_t q = (wave + qi) % PF_EARLY_QUEUES;
+        const uint32_t nq = n_items > q ? (n_items - q + PF_EARLY_QUEUES - 1u) / PF_EARLY_QUEUES : 0u;
+        if (qi > 0u) {
+            uint32_t h = 0u;
+            if (lane == 0u) h = __hip_atomic_load(queue + q * PF_EARLY_QUEUE_STRIDE, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(h) >= nq) continue;
+        }
+        for (;;) {
+            uint32_t v = 0u;
+            if (lane == 0u) v = atomicAdd(queue + q * PF_EARLY_QUEUE_STRIDE, 1u);
+            const uint32_t k = __builtin_amdgcn_readfirstlane(v);
+            if (k >= nq) break;
+            const uint32_t item = k * PF_EARLY_QUEUES + q;
+            const uint32_t set = __builtin_amdgcn_readfirstlane(order[item % n_sets]);
+            const uint32_t group = item / n_sets;
+            pf_census_set* cs = state + set;
+            if (deadline_ticks && !cut && __builtin_amdgcn_s_memrealtime() - t0 > deadline_ticks) cut = 1u;
+            if (cut) {
+                if (lane == 0u) atomicOr(&cs->cut, 1u);
+                continue;
+            }
+            CensusRows R;
+            R.n_sites = __builtin_amdgcn_readfirstlane(cs->n_sites);
+            R.holds = rows + __builtin_amdgcn_readfirstlane(cs->row_off);
+            R.alive = R.holds + R.n_sites;
+            uint32_t* sole = R.alive + R.n_sites;
+            const uint32_t cand = group * 64u + lane;
+            const bool active = cand < budget;
+            uint32_t complete = 0, fails = 0;
+            uint64_t lane_ops = 0;
+            (void)run_program<MODE_CENSUS, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), cand,
+                                                 active, 0u, nullptr, 0u, exp_tbl, &complete, &lane_ops, &prof,
+                                                 &fails, &R);
+            const uint32_t nf = fails >> 16, last = fails & 0xffffu;
+            if (active && nf == 1u && last < R.n_sites) atomicAdd(sole + last, 1u);
+            uint64_t key = active ? ((uint64_t)nf << 32) | (uint64_t)cand : ~0ull;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(key >> 32), o) << 32) |
+                                       (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)key, o);
+                key = other < key ? other : key;
+            }
+            if (lane == 0u) atomicMin(&cs->best, (unsigned long long)key);
+            decided += __popcll(pf::wave_mask(active));
+        }
+    }
+    if (lane == 0) {
+        unsigned long long* cl = counters + PF_COUNTER_OFF / 8 + (wave % PF_COUNTER_STRIPES) * 16u;
+        if (decided) {  // no short-circuit in a census: every decided lane ran the whole program
+            atomicAdd(cl + 0, (unsigned long long)decided);
+            atomicAdd(cl + 1, (unsigned long long)decided);
+        }
+        if (cut) atomicAdd(cl + 3, 1ull);
+    }
+}
+
+#define PF_CENSUS_PARAMS                                                                      \
+    const pf_set_desc *__restrict__ descs, const uint32_t *__restrict__ order, uint32_t n_sets, \
+        const uint4 *__restrict__ code, const uint32_t *__restrict__ consts,                   \
+        const uint4 *__restrict__ schema, const uint32_t *__restrict__ parents, uint64_t gseed, \
+        uint32_t budget, uint32_t groups, uint64_t deadline_ticks, uint64_t *__restrict__ t0_slot, \
+        pf_census_set *__restrict__ state, uint32_t *__restrict__ rows,                        \
+        unsigned long long *__restrict__ counters, uint32_t *__restrict__ queue
+#define PF_CENSUS_ARGS                                                                        \
+    descs, order, n_sets, code, consts, schema, parents, gseed, budget, groups, deadline_ticks, \
+        t0_slot, state, rows, counters, queue
+
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_census_kernel(PF_CENSUS_PARAMS) {
+    census_body<PF_NW_NARROW + 1>(PF_CENSUS_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_census_r16_kernel(PF_CENSUS_PARAMS) {
+    census_body<16>(PF_CENSUS_ARGS);
 }
 
 // ---- explicit-assignment evaluation (SoA [var][limb][cand]) --------------------------

@@ -54,6 +54,25 @@ class ClimbResult:
         return self.status == CLIMB_WITNESS
 
 
+@dataclass
+class CensusResult:
+    """Engine.census: one entry per requested set, in request order (include/pf_bytecode.h,
+    census contract)."""
+    holds: list              # per set: uint32 [n_sites] candidates at which the site holds
+    alive: list              # per set: uint32 [n_sites] candidates at which sites 0..j all hold
+    sole: list               # per set: uint32 [n_sites] candidates whose only failing site is j
+    best_fails: np.ndarray   # uint32 the fewest failing sites of any candidate
+    best_cand: np.ndarray    # uint32 the smallest candidate index with so few
+    status: np.ndarray       # uint32 ir.CENSUS_DONE / CENSUS_CUT
+    evals: int = 0
+    kernel_ms: float = 0.0
+    timed_out: bool = False
+
+    @property
+    def sat(self) -> np.ndarray:
+        return self.best_fails == 0
+
+
 class DeviceBatch:
     """A :class:`~mythril_amd.ir.Batch` resident in one device's HBM (pf_batch_create_on)."""
 
@@ -246,6 +265,44 @@ class Engine:
                 cut = cut or bool(st.timed_out)
             base += len(d)
         return ClimbResult(status, score, rnd, values, evals, ms, cut)
+
+    def site_counts(self, db: DeviceBatch, set_ids: Sequence[int]) -> np.ndarray:
+        """The assert sites of the given sets' device programs (pf_batch_site_counts)."""
+        ids = np.ascontiguousarray(set_ids, dtype=np.uint32)
+        out = np.zeros(max(len(ids), 1), dtype=np.uint32)
+        if len(ids):
+            _lib.check(_lib.lib().pf_batch_site_counts(db.handle, _lib.ptr_u32(ids), len(ids), _lib.ptr_u32(out)),
+                       "pf_batch_site_counts")
+        return out[:len(ids)]
+
+    def census(self, db: DeviceBatch, set_ids: Sequence[int], budget: int = 65536, seed: int = 0,
+               timeout_ms: int = 0) -> CensusResult:
+        """What blocks the given sets (pf_census_batch; include/pf_bytecode.h, census contract):
+        per assert site of the device program, how many of the plain search's candidates
+        [0, budget) under ``seed`` hold there, are still alive there, and fail there alone — and
+        the nearest miss.  A diagnostic call: nothing the search or the climb reads changes."""
+        ids = np.ascontiguousarray([int(s) & 0xFFFFFFFF for s in set_ids], dtype=np.uint32)
+        n = len(ids)
+        # an id out of range is pf_census_batch's error: count its row as empty here
+        known = [int(s) for s in ids if s < len(db)]
+        cnt = dict(zip(known, self.site_counts(db, known).tolist())) if known else {}
+        ks = [cnt.get(int(s), 0) for s in ids]
+        total = sum(ks)
+        rows = [np.zeros(max(total, 1), dtype=np.uint32) for _ in range(3)]
+        bf, bc, status = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        st = _lib.pf_stats()
+        _lib.check(_lib.lib().pf_census_batch(db.handle, seed, budget, timeout_ms,
+                                             _lib.ptr_u32(ids) if n else None, n, *(_lib.ptr_u32(r) for r in rows),
+                                             _lib.ptr_u32(bf), _lib.ptr_u32(bc), _lib.ptr_u32(status),
+                                             ctypes.byref(st)), "pf_census_batch")
+        cols = [[], [], []]
+        off = 0
+        for k in ks:
+            for c, r in zip(cols, rows):
+                c.append(r[off:off + k].copy())
+            off += k
+        return CensusResult(cols[0], cols[1], cols[2], bf[:n], bc[:n], status[:n], st.cands_decided,
+                            st.kernel_ms, bool(st.timed_out))
 
     def materialize_limbs(self, db: DeviceBatch, set_ids: Sequence[int], cand_ids: Sequence[int],
                           seed: int = 0) -> np.ndarray:

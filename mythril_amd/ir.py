@@ -156,6 +156,19 @@ def climb_round_seed(seed: int, r: int) -> int:
     """Global seed of round ``r`` of a climb with global seed ``seed``."""
     return (seed + (r + 1) * CLIMB_SEED_MUL) & 0xFFFFFFFFFFFFFFFF
 
+# ---- census contract (include/pf_bytecode.h) ----------------------------------------
+# A census counts at the assert sites of a set's device program, over the plain search's own
+# candidates [0, budget) and with no short-circuit: holds[j] (site j true), alive[j] (sites 0..j
+# all true; the last entry is the number of witnesses), sole[j] (j the only failing site), and
+# the nearest miss: the fewest failing sites of any candidate (best_fails) and the smallest
+# candidate index with so few (best_cand) — best_fails == 0 exactly when the search finds a
+# witness, best_cand then its found[s].  A set the device deadline cut reports zeros, and
+# CENSUS_UNKNOWN for best_fails and best_cand.
+CENSUS_DONE = 0       # pf_census_status
+CENSUS_CUT = 1
+CENSUS_MAX_SITES = 0xFFFF
+CENSUS_UNKNOWN = 0xFFFFFFFF
+
 # ---- algorithmic int32-op cost table (SURVEY.md §8(d)) -----------------------------
 # Ops not in the table (moves, constant loads, candidate generation) cost 0: they are
 # bookkeeping, not constraint arithmetic.  Width-generic ops scale by ceil(w/32)/8.

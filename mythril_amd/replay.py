@@ -221,12 +221,42 @@ def write_certificate(path: str, text: str, query: smtlib.Query, model) -> None:
 
 
 # ---- the replay ---------------------------------------------------------------------------
+EXPLAIN_TERM_CHARS = 160    # a conjunct's s-expression in an --explain report is cut here
+
+
+def explanation_lines(name: str, ex) -> List[str]:
+    """The ``--explain`` report of one undischarged dump (``ex``: its
+    ``gpu_check.SetExplanation``): per bucket its outcome and, for a miss, the blocking conjuncts
+    — those that fail for some candidate — most blocking first (by ``alive``, then ``sole``),
+    each s-expression cut at EXPLAIN_TERM_CHARS, then the nearest miss."""
+    lines = [f"{name}: {ex.outcome}"]
+    for k, b in enumerate(ex.buckets):
+        lines.append(f"bucket {k}: {b.outcome} ({len(b.constraints)} conjuncts)")
+        if b.outcome != "miss":
+            continue
+        folded = sum(1 for r in b.rows if r.folded)
+        lines.append(f"  candidates {b.budget}, roots {len(b.rows)} ({folded} folded), "
+                     f"nearest miss fails {b.best_fails} at candidate {b.best_cand}")
+        for r in b.blocking():
+            text = r.label
+            if len(text) > EXPLAIN_TERM_CHARS:
+                text = text[:EXPLAIN_TERM_CHARS] + "..."
+            lines.append(f"  alive {r.alive:>8} sole {r.sole:>8} holds {r.holds:>8}  {text}")
+        for sym, val in sorted(b.nearest.items()):
+            if len(sym) > EXPLAIN_TERM_CHARS:
+                sym = sym[:EXPLAIN_TERM_CHARS] + "..."
+            lines.append(f"  nearest {sym} = {hex(val)}")
+    return lines
+
+
 def replay_dir(path: str, config=None, models_dir: Optional[str] = None,
-               workers: Optional[int] = None) -> ReplayReport:
+               workers: Optional[int] = None, explain_dir: Optional[str] = None) -> ReplayReport:
     """Answer every ``*.smt2`` dump of directory ``path`` (see the module docstring).
     ``config``: a ``gpu_check.GpuConfig`` (budget, timeout, hints …), default
     ``gpu_check.CONFIG``; ``models_dir``: where to write the witness certificates;
-    ``workers``: reader processes, never more than :func:`max_workers`."""
+    ``workers``: reader processes, never more than :func:`max_workers`; ``explain_dir``: where
+    to write ``<name>.explain.txt`` for every dump left ``unknown`` (gpu_check.explain_sets: the
+    conjuncts that block it) — the answers are what they are without it."""
     from . import engine as E
     from .smt import gpu_check
 
@@ -298,6 +328,15 @@ def replay_dir(path: str, config=None, models_dir: Optional[str] = None,
                     fr.cls = f"error: {err}"
             fr.ms += share + (time.perf_counter() - t1) * 1e3
         rep.phase_s["recheck"] += time.perf_counter() - t0
+        left = [fr for fr in members if fr.cls == "unknown"]
+        if explain_dir is not None and left:
+            # after the group's answers are in: explain_sets records nothing, and the caches are
+            # cleared before the next group anyway
+            os.makedirs(explain_dir, exist_ok=True)
+            exs = gpu_check.explain_sets([fr.query.assertions for fr in left], registry=reg, cfg=cfg)
+            for fr, ex in zip(left, exs):
+                with open(os.path.join(explain_dir, fr.name[:-len(".smt2")] + ".explain.txt"), "w") as f:
+                    f.write("\n".join(explanation_lines(fr.name, ex)) + "\n")
     gpu_check.reset_cache()
 
     if models_dir is not None:
@@ -343,6 +382,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--budget", type=int, default=gpu_check.CONFIG.budget, help="candidates per bucket")
     ap.add_argument("--timeout-ms", type=int, default=gpu_check.CONFIG.timeout_ms)
     ap.add_argument("--models", metavar="DIR", help="write <name>.model.smt2 witness certificates here")
+    ap.add_argument("--explain", metavar="DIR",
+                    help="write <name>.explain.txt here for every dump that was not discharged: the conjuncts "
+                         "that block it, by a census of the search's own candidates")
     ap.add_argument("--workers", type=int, default=None, help="reader processes (at most min(16, CPUs allowed))")
     ap.add_argument("--climb", metavar="ROUNDS[:CANDIDATES]", type=_climb_arg, default=None,
                     help="climb the buckets the search finds nothing for: ROUNDS scored rounds of CANDIDATES "
@@ -358,7 +400,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.climb is not None:
         cfg = replace(cfg, climb_rounds=args.climb[0],
                       climb_candidates=args.climb[1] if args.climb[1] is not None else cfg.climb_candidates)
-    rep = replay_dir(args.dir, config=cfg, models_dir=args.models, workers=args.workers)
+    # without the flag the call is what it was
+    more = {"explain_dir": args.explain} if args.explain is not None else {}
+    rep = replay_dir(args.dir, config=cfg, models_dir=args.models, workers=args.workers, **more)
     lines = rep.json_lines()
     if args.out:
         with open(args.out, "w") as f:

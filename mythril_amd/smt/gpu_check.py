@@ -796,3 +796,176 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
             STATS.evals += res.cands_decided + climb_evals
         STATS.host_s += time.perf_counter() - t0 - ((res.kernel_ms + climb_ms) / 1e3 if res is not None else 0.0)
     return out
+
+
+# ---- explain: what blocks the sets the search misses --------------------------------------
+
+@dataclass
+class ConjunctRow:
+    """One root of a missed bucket's lowering: a conjunct of the bucket, or a side constraint
+    of the lowering (``term`` None).  ``folded``: the device program has no site for it (the
+    fold pass proved it); else the census counts of its site."""
+    term: Optional[T.Term]
+    folded: bool = False
+    holds: int = 0           # candidates at which the conjunct holds
+    alive: int = 0           # candidates at which every site up to its own holds
+    sole: int = 0            # candidates at which it is the only failing one
+
+    @property
+    def label(self) -> str:
+        return "side" if self.term is None else T.to_sexpr(self.term)
+
+
+@dataclass
+class BucketExplanation:
+    """outcome: "witness", "miss", "cut" (the device deadline cut the search or the census) or
+    "lowering: <reason>".  For a miss: one row per root of the lowering (Dag.roots order: the
+    bucket's conjuncts, then the side constraints), the candidates counted, and the nearest
+    miss — the fewest failing sites of any candidate, and that candidate's values of the
+    symbols the conjuncts it fails read ({symbol or term: value})."""
+    constraints: Tuple[T.Term, ...]
+    outcome: str
+    rows: List[ConjunctRow] = field(default_factory=list)
+    budget: int = 0
+    best_fails: Optional[int] = None
+    best_cand: Optional[int] = None
+    nearest: Dict[str, int] = field(default_factory=dict)
+
+    def blocking(self) -> List[ConjunctRow]:
+        """The rows that fail somewhere, most blocking first: by alive, then by sole."""
+        rows = [r for r in self.rows if not r.folded and r.holds < self.budget]
+        return sorted(rows, key=lambda r: (r.alive, r.sole))
+
+
+@dataclass
+class SetExplanation:
+    outcome: str                       # the worst of its buckets': lowering > cut > miss > witness
+    buckets: List[BucketExplanation] = field(default_factory=list)
+
+
+def _subterms(t: T.Term) -> set:
+    seen, stack = set(), [t]
+    while stack:
+        x = stack.pop()
+        if x in seen:
+            continue
+        seen.add(x)
+        stack.extend(a for a in getattr(x, "args", ()) if isinstance(a, T.Term))
+    return seen
+
+
+def _term_name(t: T.Term) -> str:
+    return t.val if t.op in ("var", "bvar") else T.to_sexpr(t)
+
+
+def distinct_buckets(sets: Sequence[Sequence[T.Term]], reg: UFRegistry, cfg: GpuConfig):
+    """check_sets' front half without its caches: (per set its bucket keys — None for a set with
+    a literal false conjunct —, {bucket: BucketExplanation} of the buckets that do not lower,
+    programs, witness metadata and bucket keys of those that do), every distinct bucket once, with
+    check_sets' bucketing, parent models (read, not recorded), hints and lowering."""
+    per_set: List[Optional[List[tuple]]] = []
+    order: List[tuple] = []
+    seen = set()
+    for cs in sets:
+        cs = [c for c in cs if c is not T.TRUE]
+        if any(c is T.FALSE for c in cs):
+            per_set.append(None)
+            continue
+        bks = None
+        if cfg.split and _NATIVE_TERMS:
+            from . import native_terms
+
+            bks = native_terms.buckets(cs)
+        if bks is None:
+            bks = buckets(cs) if cfg.split else [cs]
+        ks = [tuple(b) for b in bks]
+        per_set.append(ks)
+        for k in ks:
+            if k not in seen:
+                seen.add(k)
+                order.append(k)
+    done: Dict[tuple, BucketExplanation] = {}
+    progs, lows, keys = [], [], []
+    for k in order:
+        try:
+            parent = _recent_parent(list(k)) if cfg.parents else None
+            lo, prog = _lower_bucket(list(k), reg, parent, cfg.hints)
+        except (LoweringError, ValueError, OverflowError, RecursionError) as e:
+            why = str(e) if isinstance(e, LoweringError) else f"{type(e).__name__}: {e}"
+            done[k] = BucketExplanation(k, "lowering: " + why.split(":")[0][:60])
+            continue
+        progs.append(prog)
+        lows.append(lo)
+        keys.append(k)
+    return per_set, done, progs, lows, keys
+
+
+def explain_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] = None,
+                 cfg: Optional[GpuConfig] = None) -> List[SetExplanation]:
+    """Why the search misses what it misses.  Buckets, lowering, hints and parent models are
+    check_sets'; every distinct bucket is searched once (the plain search: no climb), and every
+    bucket left without a witness goes through a census (include/pf_bytecode.h, census contract)
+    on the batch still resident.  A diagnostic call: it reads the recent-values tables for its
+    parent models but records nothing — the witness cache, the negative cache, STATS and the
+    recent values are left as found, so explaining changes no later answer."""
+    from .. import _lib
+    from ..engine import get_engine
+
+    cfg = cfg or CONFIG
+    reg = registry or DEFAULT_REGISTRY
+    per_set, done, progs, lows, keys = distinct_buckets(sets, reg, cfg)
+    if progs:
+        eng = get_engine()
+        db = eng.upload(progs)
+        try:
+            res = eng.check(db, budget=cfg.budget, seed=cfg.seed, flags=cfg.flags, timeout_ms=cfg.timeout_ms)
+            missed = [i for i in range(len(progs)) if res.found[i] == 0xFFFFFFFF]
+            for i in range(len(progs)):
+                if res.found[i] != 0xFFFFFFFF:
+                    done[keys[i]] = BucketExplanation(keys[i], "witness")
+            if res.timed_out:
+                for i in missed:
+                    done[keys[i]] = BucketExplanation(keys[i], "cut")
+                missed = []
+            if missed:
+                cen = eng.census(db, missed, budget=cfg.budget, seed=cfg.seed, timeout_ms=cfg.timeout_ms)
+                batch = db.batch
+                site_map = _lib.device_sites(batch.code, batch.consts, batch.descs)
+                for j, i in enumerate(missed):
+                    if int(cen.status[j]) != ir.CENSUS_DONE:
+                        done[keys[i]] = BucketExplanation(keys[i], "cut")
+                        continue
+                    d = batch.descs[i]
+                    ops = np.asarray(batch.code[int(d[0]):int(d[0]) + int(d[1]), 0]) & 0xFF
+                    n_roots = int((ops == ir.ASSERT).sum())
+                    cs = list(keys[i])
+                    rows = [ConjunctRow(cs[r] if r < len(cs) else None, folded=True) for r in range(n_roots)]
+                    for site, r in enumerate(site_map[i].tolist()):
+                        rows[r] = ConjunctRow(rows[r].term, False, int(cen.holds[j][site]),
+                                              int(cen.alive[j][site]), int(cen.sole[j][site]))
+                    ex = BucketExplanation(keys[i], "miss", rows, cfg.budget, int(cen.best_fails[j]),
+                                           int(cen.best_cand[j]))
+                    # the nearest candidate's values, of the symbols its failing conjuncts read
+                    vals = eng.materialize(db, [i], [ex.best_cand], seed=cfg.seed)[0]
+                    w = Witness(lows[i], [int(v) for v in vals], reg)
+                    reads: set = set()
+                    for c in cs:
+                        try:
+                            if not w.ev(c):
+                                reads |= _subterms(c)
+                        except Exception:      # a term the host interpretation declines: show its symbols
+                            reads |= _subterms(c)
+                    ex.nearest = {_term_name(t): int(v) for t, v in zip(lows[i].var_terms, vals) if t in reads}
+                    done[keys[i]] = ex
+        finally:
+            db.free()
+    rank = {"witness": 0, "miss": 1, "cut": 2}
+    out = []
+    for ks in per_set:
+        if ks is None:
+            out.append(SetExplanation("miss", []))     # a literal false conjunct: nothing to search
+            continue
+        bs = [done[k] for k in ks]
+        worst = max(bs, key=lambda b: rank.get(b.outcome, 3), default=None)
+        out.append(SetExplanation(worst.outcome if worst else "witness", bs))
+    return out

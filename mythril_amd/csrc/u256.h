@@ -699,9 +699,12 @@ PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, bool want_b
 // Level i lives mod 2^P_i, P_i = 256 - (valuation of d_1 ... d_{i-1}), on ceil(P_i / 32) limbs;
 // below 8 limbs its product is scanned by column with K_i as the accumulator's starting value
 // (tmul_add), at 8 limbs it is mul256 and one add256.
-// t_M is needed mod 2^(254-M) only: the M-1 recurrence steps are truncated squares of
-// shrinking width (sqr256 while the width is 8 limbs).  The windowed left-to-right loop then
-// runs over M exponent bits instead of 256.
+// Neither t nor the per-level shift S_i is ever formed.  x = b^(2^M) - 1 mod 2^256 is b^2
+// squared M - 1 times (sqr256) less one, which is t_M mod 2^(254-M) — all of t_M that can
+// matter — already shifted by M + 2; the chain carries the factor as ((n - i + 1) t) << (M + 2),
+// a multiple of x that steps by x, and the levels' values scaled by the powers of two that
+// the factors are too large by (the scale schedule, below at exp_sched).  The windowed
+// left-to-right loop then runs over M exponent bits instead of 256.
 // Even b: b^e = 0 for e >= 256 (2-adic valuation >= e), else e = e0 + 2^M n with n the
 // high part of a value < 256 — M >= 8 makes n = 0 and b^e = b^e0.
 // (tools/u256_fuzz.py checks this against Python's pow on the host build.)
@@ -716,72 +719,6 @@ PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, bool want_b
 PF_INL uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t s) {
     return (uint32_t)((((uint64_t)hi << 32) | lo) >> s);
 }
-
-// out = a^2 mod 2^(32 L): cross products once, doubled, plus the diagonal
-template <int L>
-PF_INL void tsqr(const uint32_t* a, uint32_t* out) {
-    uint32_t r[L];
-#pragma unroll
-    for (int i = 0; i < L; i++) r[i] = 0u;
-#pragma unroll
-    for (int i = 0; 2 * i + 1 < L; i++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int j = i + 1; i + j < L; j++) {
-            c = (uint64_t)a[i] * a[j] + (uint64_t)r[i + j] + (c >> 32);
-            r[i + j] = (uint32_t)c;
-        }
-    }
-#pragma unroll
-    for (int i = L - 1; i >= 1; i--) r[i] = funnel(r[i], r[i - 1], 31u);
-    r[0] <<= 1;
-    uint32_t d[L];
-#pragma unroll
-    for (int i = 0; 2 * i < L; i++) {
-        const uint64_t q = (uint64_t)a[i] * a[i];
-        d[2 * i] = (uint32_t)q;
-        if (2 * i + 1 < L) d[2 * i + 1] = (uint32_t)(q >> 32);
-    }
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < L; i++) {
-        uint32_t co;
-        out[i] = __builtin_addc(r[i], d[i], c, &co);
-        c = co;
-    }
-}
-
-// recurrence steps k in [k0, k1) (k / 32 == Q) on t mod 2^T (TL limbs, top limb mask TM):
-// t += (t^2 mod 2^(32(TL-Q))) << (k + 1)
-template <int TL, uint32_t TM, int Q>
-PF_INL void t_steps(uint32_t* t, uint32_t k0, uint32_t k1) {
-    constexpr int L = TL - Q;
-#pragma unroll 1
-    for (uint32_t k = k0; k < k1; k++) {
-        uint32_t sq[L];
-        if constexpr (L == 8) {  // the column-scanned square
-            u256 a;
-#pragma unroll
-            for (int i = 0; i < 8; i++) a.l[i] = t[i];
-            const u256 s = sqr256(a);
-#pragma unroll
-            for (int i = 0; i < 8; i++) sq[i] = s.l[i];
-        } else {
-            tsqr<L>(t, sq);
-        }
-        const uint32_t sh = 32u - (k + 1u - 32u * Q);  // r = k+1-32Q in [1, 32] -> sh in [0, 31]
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = Q; i < TL; i++) {
-            const uint32_t lo = i > Q ? sq[i > Q ? i - Q - 1 : 0] : 0u;
-            uint32_t co;
-            t[i] = __builtin_addc(t[i], funnel(sq[i - Q], lo, sh), c, &co);
-            c = co;
-        }
-        t[TL - 1] &= TM;
-    }
-}
-
 
 constexpr int v2c(int i) { return (i & 1) ? 0 : 1 + v2c(i >> 1); }
 constexpr int v2fact(int j) { return j <= 1 ? 0 : v2c(j) + v2fact(j - 1); }
@@ -862,77 +799,139 @@ PF_INL u256 tmul_add(const u256& a, const u256& b, const k256& k) {
     }
 }
 
-// a * b mod 2^(32 L)
-template <int L>
-PF_INL u256 tmul(const u256& a, const u256& b) {
-    if constexpr (L >= 8)
-        return mul256(a, b);
-    else
-        return tmul_add<L, L, 0u, 0u, 0u, 0u, 0u, 0u, 0u>(a, b, k256{});
-}
-
-// a - b * c mod 2^(32 L), c a small constant
-template <int L>
-PF_INL u256 sub_mul_small(const u256& a, const u256& b, uint32_t c) {
-    u256 r = zero256();
-    uint32_t carry = 0, bw = 0;
+// a - c mod 2^256, c a small constant
+PF_INL u256 sub_small256(const u256& a, uint32_t c) {
+    u256 r;
+    uint32_t bw = 0;
 #pragma unroll
-    for (int i = 0; i < L; i++) {
-        const uint64_t p = (uint64_t)b.l[i] * c + carry;
-        carry = (uint32_t)(p >> 32);
+    for (int i = 0; i < 8; i++) {
         uint32_t bo;
-        r.l[i] = __builtin_subc(a.l[i], (uint32_t)p, bw, &bo);
+        r.l[i] = __builtin_subc(a.l[i], i == 0 ? c : 0u, bw, &bo);
         bw = bo;
     }
     return r;
 }
 
-// a << S mod 2^(32 L), S a compile-time constant
+// limbs 0 .. L-1 of a >> S, S in [0, 31] a compile-time constant (limbs >= L of the result zero)
 template <int S, int L>
-PF_INL u256 shl_const(const u256& a) {
-    constexpr int LS = S / 32, BS = S % 32;
+PF_INL u256 shr_const(const u256& a) {
+    static_assert(S >= 0 && S < 32 && L >= 1 && L <= 8, "shape");
     u256 r = zero256();
 #pragma unroll
-    for (int i = LS; i < L; i++) {
-        const uint32_t hi = a.l[i - LS];
-        const uint32_t lo = i - LS - 1 >= 0 ? a.l[i - LS - 1 >= 0 ? i - LS - 1 : 0] : 0u;
-        r.l[i] = BS ? funnel(hi, lo, 32 - BS) : hi;
-    }
+    for (int i = 0; i < L; i++) r.l[i] = S ? funnel(i + 1 < 8 ? a.l[i + 1 < 8 ? i + 1 : 0] : 0u, a.l[i], S) : a.l[i];
     return r;
 }
 
-// Horner level I of sum_j C(n, j) x^j in its division-free form: v_I = K_I + d_I v_{I+1} with
-// d_I = ((n - I + 1) t) << S_I and v_{J+1} = K_{J+1} (see above exp256_split), computed mod
-// 2^P_I (P_I = 256 - prefix_val(I): bits above are multiplied out of range by d_1..d_{I-1})
-// on L = ceil(P_I / 32) limbs.  P_{I+1} = P_I - S_I, so the inner value's L_{I+1} limbs are
-// all that d_I's S_I trailing zeros leave in range.  g carries (n - I + 1) t from level to
-// level: it enters the innermost level as (n - J + 1) t and every level on the way out adds t
-// (on all 8 limbs: the outer levels read more of them than the inner ones), so n t is dead once
-// the chain starts and no level multiplies t by its index.
+// k << s mod 2^(32 limbs), s in [0, 31]
+constexpr k256 k_shl(const k256& k, int s, int limbs) {
+    k256 r{};
+    for (int i = 0; i < limbs; i++) {
+        const uint64_t w = ((uint64_t)k.l[i] << 32) | (i ? k.l[i - 1] : 0u);
+        r.l[i] = (uint32_t)(w >> (32 - s));
+    }
+    return r;
+}
+// the condition under which tmul_add's columns take k's limbs as literals (u256_cols.h, tmulk:
+// limb c >= 2 plus the column's c - 1 carries must fit 32 bits); the 8-limb levels add k whole
+constexpr bool exp_literal_ok(const k256& k, int limbs) {
+    if (limbs >= 8) return true;
+    for (int c = 2; c < limbs; c++)
+        if (k.l[c] > 0xFFFFFFFFu - (uint32_t)(c - 1)) return false;
+    return true;
+}
+
+// ---- the chain's scale schedule --------------------------------------------------------
+// The factor of level I is d_I = ((n - I + 1) t) << (M + 2 - v2(I)): shifted per level, that is
+// one funnel shift per limb per level.  Instead the chain carries G_I = ((n - I + 1) t) << (M + 2)
+// (d_I = G_I >> v2(I); stepping a level adds t << (M + 2) = b^(2^M) - 1) and the scaled values
+// w_I = 2^(c_I) v_I, which obey
+//   w_I = (K_I << c_I) + G_I w_{I+1},  c_I = c_{I+1} + v2(I),  c_{J+1} = 0
+// with no shift at all, as long as the P_I + c_I bits of w_I that matter fit the level's
+// 32 L_I (G_I's M + 2 trailing zeros make the product read P_{I+1} + c_{I+1} bits of w_{I+1}).
+// Where they do not, w_{I+1} is un-scaled first (>> c_{I+1}: exact, its low bits are zero) and
+// c_I = v2(I); where that does not fit either, G_I is shifted down by v2(I) as well and
+// c_I = 0, which is the unscaled level.  A level whose shifted addend fails the literal
+// condition of tmul_add's columns falls through the same choices.  Level 1 has 256 bits on 8
+// limbs, so the chain always ends with c_1 = 0 and w_1 = v_1.
+constexpr int EXP_MAX_TERMS = 32;  // J = 28 at the smallest split (8)
+struct exp_sched_t {
+    int c[EXP_MAX_TERMS + 2];       // c_I, the scale of level I's value
+    bool unscale[EXP_MAX_TERMS + 2];  // level I reads w_{I+1} >> c_{I+1}
+    bool shift_g[EXP_MAX_TERMS + 2];  // level I multiplies by G_I >> v2(I)
+};
+constexpr exp_sched_t exp_sched(int m) {
+    exp_sched_t s{};
+    const int j = exp_terms(m);
+    const k256 inv = k_inv(exp_oddprod(1, j));
+    k256 e = k_small(1u);  // E_{i}, from E_{J+1} = 1 down
+    for (int i = j; i >= 1; i--) {
+        e = k_mul(e, k_small((uint32_t)(i >> v2c(i))));
+        const int p = 256 - prefix_val(m, i), l = (p + 31) / 32, v = v2c(i), cin = s.c[i + 1];
+        k256 k = k_mul(e, inv);
+        for (int q = l; q < 8; q++) k.l[q] = 0u;
+        if (p + cin + v <= 32 * l && exp_literal_ok(k_shl(k, cin + v, l), l)) {
+            s.c[i] = cin + v;
+        } else if (p + v <= 32 * l && exp_literal_ok(k_shl(k, v, l), l)) {
+            s.c[i] = v;
+            s.unscale[i] = cin != 0;
+        } else {
+            s.c[i] = 0;
+            s.unscale[i] = cin != 0;
+            s.shift_g[i] = v != 0;
+        }
+    }
+    return s;
+}
+template <int M>
+inline constexpr exp_sched_t EXP_SCHED = exp_sched(M);
+
+// Horner level I of sum_j C(n, j) x^j in its division-free, scaled form (above):
+// w_I = (K_I << c_I) + G_I w_{I+1} with w_{J+1} = K_{J+1}, computed mod 2^(P_I + c_I)
+// (P_I = 256 - prefix_val(I): bits above are multiplied out of range by d_1..d_{I-1}) on
+// L = ceil(P_I / 32) limbs.  P_{I+1} = P_I - S_I (S_I = M + 2 - v2(I)), so the inner value's
+// limbs are all that the factor's trailing zeros leave in range.  G carries
+// ((n - I + 1) t) << (M + 2) from level to level: it enters the innermost level for I = J and
+// every level on the way out adds T = t << (M + 2) = b^(2^M) - 1 (on all 8 limbs: the outer
+// levels read more of them than the inner ones), so no level multiplies t by its index or
+// shifts it.
 template <int M, int I, int J>
-PF_INL u256 horner(u256& g, const u256& tt) {
-    constexpr int S = M + 2 - v2c(I);                 // x / 2^v2(I) = 2^S t
+PF_INL u256 horner(u256& G, const u256& T) {
+    static_assert(J <= EXP_MAX_TERMS, "schedule size");
+    constexpr int V = v2c(I);
     constexpr int P = 256 - prefix_val(M, I);
     constexpr int L = (P + 31) / 32;
-    constexpr k256 K = exp_addend(I, J, L);
-    // limbs of v_{I+1} (P_{I+1} = P - S) that the product reads: L, or L - 1 where they are
-    // fewer (any further ones are zero)
-    constexpr int LY = (I == J || (P - S + 31) / 32 >= L || L == 1) ? L : L - 1;
+    constexpr int C = EXP_SCHED<M>.c[I];
+    constexpr bool UNSCALE = EXP_SCHED<M>.unscale[I], SHIFT_G = EXP_SCHED<M>.shift_g[I];
+    constexpr int CIN = EXP_SCHED<M>.c[I + 1];            // scale of w_{I+1} as the chain hands it up
+    constexpr int CY = UNSCALE ? 0 : CIN;                 // ... and as the product reads it
+    static_assert(C == CY + (SHIFT_G ? 0 : V) && C >= 0 && C < 32 && CIN < 32, "scale schedule");
+    static_assert(P + C <= 32 * L, "the scaled level fits its limbs");
+    static_assert(I > 1 || C == 0, "the chain ends unscaled");
+    constexpr k256 K = k_shl(exp_addend(I, J, L), C, L);
+    static_assert(exp_literal_ok(K, L), "shifted addend as column literals");
+    // limbs of w_{I+1} (P_{I+1} + its scale bits) that the product reads: L, or L - 1 where
+    // they are fewer (any further ones are zero)
+    constexpr int PY = P - (M + 2 - V);
+    constexpr int LY = (I == J || (PY + CY + 31) / 32 >= L || L == 1) ? L : L - 1;
     // the inner chain first: only its result (not this level's factor) stays live across it
     u256 inner = zero256();
     if constexpr (I < J) {
-        inner = horner<M, I + 1, J>(g, tt);
-        g = add256(g, tt);  // (n - I + 1) t from (n - I) t
+        inner = horner<M, I + 1, J>(G, T);
+        G = add256(G, T);  // ((n - I + 1) t) << (M + 2) from level I + 1's
+        if constexpr (UNSCALE) inner = shr_const<CIN, (PY + 31) / 32>(inner);
     } else {
-        constexpr k256 C = exp_addend(J + 1, J, L);
+        constexpr k256 C0 = exp_addend(J + 1, J, L);
 #pragma unroll
-        for (int i = 0; i < L; i++) inner.l[i] = C.l[i];
+        for (int i = 0; i < L; i++) inner.l[i] = C0.l[i];
     }
-    return tmul_add<L, LY, K.l[0], K.l[1], K.l[2], K.l[3], K.l[4], K.l[5], K.l[6]>(shl_const<S, L>(g), inner, K);
+    if constexpr (SHIFT_G)
+        return tmul_add<L, LY, K.l[0], K.l[1], K.l[2], K.l[3], K.l[4], K.l[5], K.l[6]>(shr_const<V, L>(G), inner, K);
+    else
+        return tmul_add<L, LY, K.l[0], K.l[1], K.l[2], K.l[3], K.l[4], K.l[5], K.l[6]>(G, inner, K);
 }
 
 // pt (profiling builds, tools/unitprof.py): s_memtime cycles of the three parts —
-// windowed b^e0, the t recurrence, the Horner chain and final product
+// windowed b^e0, the squarings up to b^(2^M), the Horner chain and final product
 PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t stride,
                          uint64_t* pt = nullptr) {
 #if defined(PF_PROFILE_UNITS) && !defined(PF_HOST_MAC)
@@ -949,10 +948,9 @@ PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t s
 #endif
     constexpr int M = PF_EXP_SPLIT;
     static_assert(M >= 8 && M <= 84, "split");
-    constexpr int T = 254 - M;              // bits of t and n
-    constexpr int TL = (T + 31) / 32;       // limbs of t
+    constexpr int T = 254 - M;              // bits of n
+    constexpr int TL = (T + 31) / 32;       // limbs of n
     constexpr uint32_t TM = (T % 32) ? ((1u << (T % 32)) - 1u) : 0xffffffffu;
-    constexpr int TB = (T + 3 + 31) / 32;   // limbs of b^2 needed for t_1
     constexpr int J = exp_terms(M);
     constexpr int WB = PF_EXP_WINDOW;       // window of the left-to-right part
     const uint32_t odd = base.l[0] & 1u;
@@ -971,41 +969,29 @@ PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t s
     const bool series = wave_any(wave_mask(odd != 0u) & ~wave_mask(iszero256(n) != 0u));
     u256 r;
     if constexpr (M <= 32 && WB == 2)
-        r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, series && TB == 8, tbl, stride);
+        r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, series, tbl, stride);
     else
         r = exp256<WB>(base, e0, nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
     PF_EXP_STAMP(0)
     if (series) {
-        // b^e0 waits in the LDS table's entry 1 (base^1, no longer needed) while the t
-        // recurrence and the Horner chain run: 8 VGPRs fewer at their peak
+        // b^e0 waits in the LDS table's entry 1 (base^1, no longer needed) while the
+        // squarings and the Horner chain run: 8 VGPRs fewer at their peak
         tbl_put(tbl, stride, 1u, r);
-        // t_1 = (b^2 - 1) / 8 mod 2^T
-        uint32_t t[TL];
-        {
-            uint32_t sq[TB];
-            if constexpr (M <= 32 && WB == 2 && TB == 8) {
-                // b^2 mod 2^256 is the window table's entry 2
-                const u256 b2 = tbl_get(tbl, stride, 2u);
-#pragma unroll
-                for (int i = 0; i < TB; i++) sq[i] = b2.l[i];
-            } else {
-                tsqr<TB>(base.l, sq);
-            }
-            sq[0] -= 1u;  // b odd -> b^2 odd: no borrow
-#pragma unroll
-            for (int i = 0; i < TL; i++) t[i] = funnel(i + 1 < TB ? sq[i + 1 < TB ? i + 1 : 0] : 0u, sq[i], 3u);
-            t[TL - 1] &= TM;
-        }
-        t_steps<TL, TM, 0>(t, 1u, M < 32 ? (uint32_t)M : 32u);
-        if (M > 32) t_steps<TL, TM, 1>(t, 32u, M < 64 ? (uint32_t)M : 64u);
-        if (M > 64) t_steps<TL, TM, 2>(t, 64u, (uint32_t)M);
-        u256 tt = zero256();
-#pragma unroll
-        for (int i = 0; i < TL; i++) tt.l[i] = t[i];
+        // X = b^(2^M) - 1 = t_M << (M + 2) mod 2^256, the chain's step: b^2 (the window
+        // table's entry 2 where there is one) squared M - 1 times; b odd: no borrow
+        u256 X;
+        if constexpr (M <= 32 && WB == 2)
+            X = tbl_get(tbl, stride, 2u);
+        else
+            X = sqr256(base);
+#pragma unroll 1
+        for (int k = 1; k < M; k++) X = sqr256(X);
+        X.l[0] -= 1u;
         PF_EXP_STAMP(1)
-        const u256 nt = tmul<(256 - (M + 2) + 31) / 32>(n, tt);
-        u256 g = sub_mul_small<8>(nt, tt, (uint32_t)(J - 1));  // (n - J + 1) t, the innermost level's
-        u256 h = horner<M, 1, J>(g, tt);
+        // the chain's innermost factor G_J = (n - J + 1) X: one borrow chain (mod 2^256: the
+        // product is the same) and one product
+        u256 G = mul256(sub_small256(n, (uint32_t)(J - 1)), X);
+        u256 h = horner<M, 1, J>(G, X);
         u256 one = zero256();  // even base: n != 0 means e >= 256 -> result 0 below
         one.l[0] = 1u;
         h = sel256(odd, h, one);

@@ -15,6 +15,8 @@
  *                         turns a witness index into concrete variable values
  *   pf_eval_assignments   z3 ModelRef.eval(expr, model_completion=True) over a batch of
  *                         explicit models (mythril/support/support_utils.py:63-67)
+ *   pf_eval_batch         the same loop with the caller's own models against every set of a
+ *                         resident batch in one call (one bit per set and model)
  *   pf_keccak256_batch    eth_hash keccak via support_utils.sha3 (support_utils.py:93-101) as
  *                         called by KeccakFunctionManager.find_concrete_keccak
  *                         (keccak_function_manager.py:57-69) and get_code_hash (:74-90)
@@ -200,6 +202,32 @@ int pf_eval_programs(int device, const uint32_t* code, size_t n_ins, const uint3
                      const uint32_t* soa, uint32_t n_cand, uint8_t* sat_out);
 int pf_eval_assignments_dev(uint64_t handle, uint32_t set, const uint32_t* d_soa,
                             uint32_t n_cand, uint8_t* d_sat_out, void* stream);
+
+/* Stream n_cand explicit assignments through the sets set_ids[0 .. n) of a resident batch in one
+ * call (include/pf_bytecode.h, stream contract): a fuzzer's corpus, a pool of models or the
+ * witnesses of an earlier transaction tried against every open state.  set_ids is a host array
+ * in both calls; d_soa / soa is [V][8][n_cand] u32 over the batch's V variables, set s reading
+ * rows descs[s].var_off .. + n_vars(s) (pf_eval_programs' layout; rows of sets not requested are
+ * never read by the kernels).  Per request i, in request order: ceil(n_cand / 64) u64 verdict
+ * words in bits (bit c & 63 of word c >> 6 = candidate c; the bits past n_cand are 0; every word
+ * is written), first[i] = the smallest satisfying candidate or 0xFFFFFFFF, count[i] = the
+ * satisfying candidates.  first and count may each be NULL, bits may be NULL when one of them is
+ * given.  flags: PF_FLAG_SHORTCIRCUIT or 0 (the verdicts are the same).  stats: evals_full,
+ * cands_decided and kernel_ms as for a full sweep, n_sat = the sets with a satisfying candidate,
+ * timed_out = 0.  An id out of range or repeated, any other flag, every output NULL: error,
+ * nothing launched; n == 0 or n_cand == 0: 0, nothing launched, no output written.
+ * pf_eval_batch_dev takes device pointers and a stream (NULL = the library stream of the batch's
+ * device) and waits for the device only when stats is given or when the request differs from
+ * the batch's last one (its tables are then uploaded); pf_eval_batch copies in and out through a
+ * pooled block and pinned staging and runs the same kernels.                                 */
+int pf_eval_batch_dev(uint64_t handle, const uint32_t* set_ids, size_t n,
+                      const uint32_t* d_soa, uint32_t n_cand, uint32_t flags,
+                      uint64_t* d_bits, uint32_t* d_first, uint32_t* d_count,
+                      pf_stats* stats, void* stream);
+int pf_eval_batch(uint64_t handle, const uint32_t* set_ids, size_t n,
+                  const uint32_t* soa, uint32_t n_cand, uint32_t flags,
+                  uint64_t* bits_out, uint32_t* first_out, uint32_t* count_out,
+                  pf_stats* stats);
 
 /* Keccak-256 (original padding) of n messages data[offsets[i] .. offsets[i+1]).           */
 int pf_keccak256_batch(const uint8_t* data, const uint64_t* offsets, size_t n, uint8_t* out32);

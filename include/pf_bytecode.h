@@ -50,7 +50,8 @@
 #define PF_EARLY_QUEUE_STRIDE 32
 #define PF_EARLY_QUEUE_OFF 512
 /* per-launch counters (evals_full, cands_decided, ops, timed-out items): PF_COUNTER_STRIPES
- * lines of 4 u64, 128 B apart, after the queue heads; a wave adds its non-zero totals
+ * lines of 4 u64 (a stream call adds a fifth, the sets with a witness), 128 B apart, after
+ * the queue heads; a wave adds its non-zero totals
  * into line wave % PF_COUNTER_STRIPES and the host sums the lines (one line took every wave's
  * atomics in series: ~60 us at the end of a 4,096-wave grid) */
 #define PF_COUNTER_STRIPES 16
@@ -397,6 +398,38 @@ enum pf_census_status {
     PF_CENSUS_CUT = 1
 };
 #define PF_CENSUS_MAX_SITES 0xffffu
+
+/* ---- stream contract ------------------------------------------------------------ */
+/* A stream call (pf_eval_batch, pf_eval_batch_dev) decides explicit assignments, read from
+ * memory, against the sets of a resident batch: nothing is generated.
+ *
+ * Input.  n_cand assignments as SoA limbs [V][8][n_cand] u32, V the batch's total variable count:
+ * limb l of variable v of candidate c is word (v * 8 + l) * n_cand + c.  Set s reads rows
+ * descs[s].var_off .. + n_vars(s), its own variables in schema order (pf_eval_programs' layout).
+ * Rows of sets that were not requested are never read.
+ *
+ * Verdict.  Candidate c's verdict on set s is the root of the set's device program under it,
+ * exactly pf_eval_assignments' semantics: a W variable's value is masked to the variable's
+ * width, a Bool variable is bit 0 of its limb 0.
+ *
+ * Request.  set_ids[0 .. n) names the sets, each at most once; the outputs are in request order.
+ *    bits    n x ceil(n_cand / 64) u64: bit c & 63 of word c >> 6 of request i is candidate c's
+ *            verdict; the bits past n_cand in the last word are 0; every word of every request
+ *            is written, so the buffer need not be cleared
+ *    first   u32 per request: the smallest satisfying candidate, 0xFFFFFFFF if there is none
+ *    count   u32 per request: the satisfying candidates
+ * first and count may each be absent; bits may be absent when one of them is given.
+ *
+ * Flags.  PF_FLAG_SHORTCIRCUIT alone is read, any other bit is an error.  With it a wave whose
+ * lanes are all false at an assert site stops there; the outputs do not depend on it.
+ *
+ * Stats.  evals_full = lanes that ran their program to its end, cands_decided = n x n_cand,
+ * kernel_ms = HIP-event time on the call's stream, n_sat = the requests with a satisfying
+ * candidate, timed_out = 0 (a stream call has no deadline).
+ *
+ * An id out of range, an id given twice, an unknown flag or no output at all is an error and
+ * nothing is launched; n == 0 or n_cand == 0 (with valid ids and flags) returns 0, launches
+ * nothing and writes no output, whatever the output pointers are.                          */
 
 /* flags for pf_check_batch */
 #define PF_FLAG_SHORTCIRCUIT 1u  /* stop a wave's set evaluation once all its lanes are false */

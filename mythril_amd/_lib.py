@@ -83,6 +83,11 @@ SIGNATURES = {
                                         ctypes.c_uint32, _u8p]),
     "pf_eval_assignments_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "pf_eval_batch_dev": (ctypes.c_int, [ctypes.c_uint64, _u32p, _sz, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(pf_stats), ctypes.c_void_p]),
+    "pf_eval_batch": (ctypes.c_int, [ctypes.c_uint64, _u32p, _sz, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                     _u64p, _u32p, _u32p, ctypes.POINTER(pf_stats)]),
     "pf_device_program": (ctypes.c_int, [_u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p, ctypes.POINTER(_sz), _u32p]),
     "pf_device_batch": (ctypes.c_int, [_u32p, _sz, _u32p, _sz, _u32p, _sz, _u32p, ctypes.POINTER(_sz), _u32p,
                                        _u32p, _sz, ctypes.POINTER(_sz)]),

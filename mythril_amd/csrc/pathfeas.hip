@@ -146,10 +146,18 @@ struct Batch {
     // long as the batch
     void* s_mem = nullptr;
     size_t s_cap = 0;
+    // stream (pf_eval_batch): d_order's host copy, and the stream block — a call's sets in launch
+    // order and their places in the request, n_sets u32 each — allocated by the batch's first
+    // stream call; e_req is what the block holds (a call with the same request uploads nothing)
+    std::vector<uint32_t> h_order;
+    void* e_mem = nullptr;
+    size_t e_cap = 0;
+    std::vector<uint32_t> e_req;
     ~Batch() {  // the device block goes back to its device's pool first (release_batch)
         if (d_mem) hipFree(d_mem);
         if (c_mem) hipFree(c_mem);
         if (s_mem) hipFree(s_mem);
+        if (e_mem) hipFree(e_mem);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
     }
@@ -219,6 +227,10 @@ void release_batch(Dev* D, Batch* B) {
     if (D && B->s_mem) {
         pool_release(D, B->s_mem, B->s_cap);
         B->s_mem = nullptr;
+    }
+    if (D && B->e_mem) {
+        pool_release(D, B->e_mem, B->e_cap);
+        B->e_mem = nullptr;
     }
     if (D) {
         std::lock_guard<std::mutex> pk(g_pool_mu);
@@ -736,6 +748,7 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         B->h_descs.assign(descs, descs + n_sets);
         B->h_wide = std::move(pp.wide);
         B->h_sites = std::move(wo.sites);
+        B->h_order = wo.order;
         B->d_mem = pool_acquire(Dv, total, &B->mem_cap);
         if (!B->d_mem) {
             delete B;
@@ -1411,6 +1424,203 @@ int pf_eval_assignments_dev(uint64_t handle, uint32_t set, const uint32_t* d_soa
     if (!D) return -1;
     if (switch_stream(D, pick_stream(D, stream))) return -1;
     return eval_launch(B, set, d_soa, n_cand, d_sat_out, pick_stream(D, stream));
+}
+
+// ---- stream: explicit assignments through every requested set (stream contract) ------------
+// What both stream entry points check before anything is launched.  -1: an error (g_err set);
+// 0: nothing to do; 1: go on.
+static int stream_check(const char* who, Batch* B, const uint32_t* set_ids, size_t n, const void* soa,
+                        uint32_t n_cand, uint32_t flags, const void* bits, const void* first, const void* count,
+                        pf_stats* stats) {
+    if (!B) return fail("%s: null batch", who);
+    if (flags & ~PF_FLAG_SHORTCIRCUIT) return fail("%s: unknown flags 0x%x (PF_FLAG_SHORTCIRCUIT only)", who, flags);
+    if (n && !set_ids) return fail("%s: null set_ids", who);
+    const size_t ns = B->n_sets;
+    std::vector<uint8_t> seen(ns, 0);
+    bool vars = false;
+    for (size_t i = 0; i < n; i++) {
+        if (set_ids[i] >= ns) return fail("%s: set %u out of range (%zu sets)", who, set_ids[i], ns);
+        if (seen[set_ids[i]]) return fail("%s: set %u requested twice", who, set_ids[i]);
+        seen[set_ids[i]] = 1;
+        vars = vars || B->h_descs[set_ids[i]].n_vars != 0;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n == 0 || n_cand == 0) return 0;  // no output has an entry to write
+    if (!bits && !first && !count) return fail("%s: every output is null", who);
+    if (vars && !soa) return fail("%s: null assignments", who);
+    const uint64_t groups = ((uint64_t)n_cand + 63u) / 64u;
+    if ((uint64_t)n * groups > 0xffffffffull) return fail("%s: %zu sets x %llu groups is too many items", who, n,
+                                                          (unsigned long long)groups);
+    return 1;
+}
+
+// work-queue items per wave slot that a stream launch aims for (stream_enqueue)
+constexpr uint64_t kStreamItemsPerWave = 32;
+
+// Enqueue one stream call on st (B's device current, the request checked): the request's tables
+// (uploaded only when they differ from the last call's), the reset, the narrow and the wide
+// launch, between B's events.
+static int stream_enqueue(Dev* D, Batch* B, const uint32_t* set_ids, size_t n, const uint32_t* d_soa,
+                          uint32_t n_cand, uint32_t flags, uint64_t* d_bits, uint32_t* d_first, uint32_t* d_count,
+                          hipStream_t st) {
+    const size_t ns = B->n_sets;
+    if (!B->e_mem) {
+        B->e_mem = pool_acquire(D, std::max<size_t>(2 * ns * 4, 256), &B->e_cap);
+        if (!B->e_mem) return fail("pf_eval_batch: hipMalloc(%zu) failed", 2 * ns * 4);
+    }
+    // this call's sets in launch order — d_order's: the 8-register ones, then the 16-register
+    // ones, each part longest first — and each one's place in the request
+    std::vector<uint32_t> place(ns, 0xffffffffu), tab(2 * n);
+    for (size_t i = 0; i < n; i++) place[set_ids[i]] = (uint32_t)i;
+    size_t k = 0, n_narrow = 0;
+    for (uint32_t s : B->h_order) {
+        if (place[s] == 0xffffffffu) continue;
+        tab[k] = s;
+        tab[n + k] = place[s];
+        n_narrow += !B->h_wide[s];
+        k++;
+    }
+    uint32_t* d_req = static_cast<uint32_t*>(B->e_mem);
+    uint32_t* d_pos = d_req + n;
+    if (tab != B->e_req) {
+        // a copy from pageable memory: drained before the table goes out of scope.  Only a call
+        // whose request differs from the batch's last one pays it.
+        B->e_req.clear();
+        HIPCHK(hipMemcpyAsync(d_req, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        B->e_req = std::move(tab);
+    }
+    const uint32_t groups = (uint32_t)(((uint64_t)n_cand + 63u) / 64u);
+    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
+    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
+    // the caller's first[], or the batch's found[] (n <= n_sets entries): the kernels count the
+    // sets with a witness through it
+    uint32_t* first = d_first ? d_first : B->d_found;
+    {
+        const uint32_t nz = PF_SCRATCH_BYTES / 4;
+        const uint32_t blocks = std::min<uint32_t>((nz + (uint32_t)n + 255u) / 256u, 1024u);
+        hipLaunchKernelGGL(pf_stream_reset_kernel, dim3(blocks), dim3(256), 0, st, B->d_scratch, nz, first, d_count,
+                           (uint32_t)n);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(B->ev0, st));
+    // PF_STREAM_CHUNK_GROUPS (read on every call, for tests and sweeps): the groups per item
+    uint64_t chunk_env = 0;
+    if (const char* e = getenv("PF_STREAM_CHUNK_GROUPS")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 1 && v <= 65536) chunk_env = (uint64_t)v;
+    }
+    for (int part = 0; part < 2; ++part) {
+        const size_t begin = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
+        if (np == 0) continue;
+        // an item is a run of per_item groups of one set: about kStreamItemsPerWave items for every
+        // wave of a chip-filling grid (the claim and the set's descriptor are paid per item, the
+        // last item of a wave is the launch's tail), one group each while the grid is not full
+        const uint64_t slots = (uint64_t)D->num_cus * g_waves_per_cu_early;
+        uint64_t per_item = std::max<uint64_t>(1, (uint64_t)np * groups / (slots * kStreamItemsPerWave));
+        if (chunk_env) per_item = chunk_env;
+        per_item = std::min<uint64_t>(per_item, groups);
+        const uint64_t items = (uint64_t)np * ((groups + per_item - 1) / per_item);
+        const uint64_t waves = std::min<uint64_t>(items, slots);
+        const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
+        hipLaunchKernelGGL(part == 0 ? pf_eval_stream_kernel : pf_eval_stream_r16_kernel, dim3(blocks),
+                           dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, d_req + begin, d_pos + begin, (uint32_t)np,
+                           B->d_code, B->d_consts, B->d_schema, d_soa, n_cand, groups, (uint32_t)per_item, flags,
+                           reinterpret_cast<unsigned long long*>(d_bits), first, d_count, d_counters,
+                           d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(B->ev1, st));
+    return 0;
+}
+
+// Wait for B's stream call on st and read its counters (line slot 4: the sets with a witness).
+static int stream_collect(Batch* B, hipStream_t st, pf_stats* stats) {
+    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
+    unsigned long long hs[PF_COUNTER_STRIPES * 16];
+    uint8_t* pin = pinned_staging(cbytes);
+    HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(hs), B->d_scratch + PF_COUNTER_OFF / 4,
+                          cbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (pin) memcpy(hs, pin, cbytes);
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
+        for (int k = 0; k < 5; k++) h[k] += hs[i * 16 + k];
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+    stats->evals_full = h[0];
+    stats->cands_decided = h[1];
+    stats->ops = 0;
+    stats->n_sat = h[4];
+    stats->kernel_ms = ms;
+    stats->timed_out = 0u;
+    return 0;
+}
+
+int pf_eval_batch_dev(uint64_t handle, const uint32_t* set_ids, size_t n, const uint32_t* d_soa, uint32_t n_cand,
+                      uint32_t flags, uint64_t* d_bits, uint32_t* d_first, uint32_t* d_count, pf_stats* stats,
+                      void* stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    const int go = stream_check("pf_eval_batch_dev", B, set_ids, n, d_soa, n_cand, flags, d_bits, d_first, d_count,
+                                stats);
+    if (go <= 0) return go;
+    Dev* D = use_dev(B->device);
+    if (!D) return -1;
+    hipStream_t st = pick_stream(D, stream);
+    if (switch_stream(D, st)) return -1;
+    if (stream_enqueue(D, B, set_ids, n, d_soa, n_cand, flags, d_bits, d_first, d_count, st)) return -1;
+    return stats ? stream_collect(B, st, stats) : 0;
+}
+
+int pf_eval_batch(uint64_t handle, const uint32_t* set_ids, size_t n, const uint32_t* soa, uint32_t n_cand,
+                  uint32_t flags, uint64_t* bits_out, uint32_t* first_out, uint32_t* count_out, pf_stats* stats) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    const int go = stream_check("pf_eval_batch", B, set_ids, n, soa, n_cand, flags, bits_out, first_out, count_out,
+                                stats);
+    if (go <= 0) return go;
+    Dev* D = use_dev(B->device);
+    if (!D) return -1;
+    hipStream_t st = D->stream;
+    if (switch_stream(D, st)) return -1;
+    // one pooled block [assignments | bits | first | count] and the pinned staging buffer for both
+    // copies (pf_eval_assignments' pattern)
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t words = ((size_t)n_cand + 63) / 64;
+    const size_t soa_bytes = soa ? B->n_vars * 8 * (size_t)n_cand * 4 : 0;
+    const size_t o_bits = al(std::max<size_t>(soa_bytes, 4)), o_first = o_bits + al(n * words * 8),
+                 o_count = o_first + al(n * 4), total = o_count + al(n * 4), out_bytes = total - o_bits;
+    size_t cap = 0;
+    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, total, &cap));
+    if (!dm) return fail("pf_eval_batch: hipMalloc(%zu) failed", total);
+    uint8_t* pin = pinned_staging(std::max(soa_bytes, out_bytes));
+    int rc = pin ? 0 : -1;
+    if (!rc && soa_bytes) {
+        memcpy(pin, soa, soa_bytes);
+        if (hipMemcpyAsync(dm, pin, soa_bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
+    }
+    if (!rc && stream_enqueue(D, B, set_ids, n, reinterpret_cast<const uint32_t*>(dm), n_cand, flags,
+                              bits_out ? reinterpret_cast<uint64_t*>(dm + o_bits) : nullptr,
+                              first_out ? reinterpret_cast<uint32_t*>(dm + o_first) : nullptr,
+                              count_out ? reinterpret_cast<uint32_t*>(dm + o_count) : nullptr, st))
+        rc = -2;
+    // the staging buffer is reused for the results: the stream orders the copy after the kernels,
+    // which ran after the copy-in
+    if (!rc && (hipMemcpyAsync(pin, dm + o_bits, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess))
+        rc = -1;
+    if (rc) {
+        // work may still be in flight on the block: freed after a full synchronisation, never
+        // pooled (the pf_materialize rule)
+        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
+        return rc == -2 ? -1 : fail("pf_eval_batch: HIP call failed");
+    }
+    if (bits_out) memcpy(bits_out, pin, n * words * 8);
+    if (first_out) memcpy(first_out, pin + (o_first - o_bits), n * 4);
+    if (count_out) memcpy(count_out, pin + (o_count - o_bits), n * 4);
+    pool_release(D, dm, cap);
+    return stats ? stream_collect(B, st, stats) : 0;
 }
 
 int pf_keccak256_batch(const uint8_t* data, const uint64_t* offsets, size_t n, uint8_t* out32) {

@@ -484,7 +484,11 @@ PF_INL u256 gen_var(const SetCtx& S, uint32_t v, uint32_t cand) {
 // its two distances beside its bit, and a failing site adds PF_CLIMB_NEAR - dt
 // MODE_CENSUS: MODE_GEN's candidates, no short-circuit, and the wave's counts taken at the assert
 // sites (include/pf_bytecode.h, census contract)
-enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2, MODE_CLIMB_TREE = 3, MODE_CENSUS = 4 };
+// MODE_STREAM: MODE_SOA's candidates under the caller's flags (include/pf_bytecode.h, stream
+// contract).  A mode of its own so that run_program<MODE_SOA, 16> keeps the callers it had, all
+// of them with flags 0: with a caller that passes variable flags, constant propagation into it
+// stops and pf_eval_soa_kernel / pf_eval_soa_sets_kernel compile to other code.
+enum Mode { MODE_GEN = 0, MODE_SOA = 1, MODE_CLIMB = 2, MODE_CLIMB_TREE = 3, MODE_CENSUS = 4, MODE_STREAM = 5 };
 
 // Where a census wave's per-site counts go: the set's holds[] and alive[] rows (n_sites u32
 // each, in the batch's census block).
@@ -837,7 +841,7 @@ PF_INL uint32_t run_program(const SetCtx& S, uint32_t cand, bool active, uint32_
             }
             case PF_U_GEN:
                 // ---- candidate generator (one site for W and B variables)
-                if (MODE != MODE_SOA) {
+                if (MODE != MODE_SOA && MODE != MODE_STREAM) {
                     z = gen_var(S, aux, cand);
                 } else {
 #pragma unroll
@@ -1668,6 +1672,126 @@ pf_eval_soa_sets_kernel(const pf_set_desc* __restrict__ descs, const uint4* __re
     uint32_t sat = run_program<MODE_SOA, 16>(S, active ? cand : 0u, active, 0u, soa_s, n_cand,
                                          exp_tbl_of(pf_exp_lds), &complete, &ops, &prof);
     if (active) out[(size_t)set * n_cand + cand] = (uint8_t)sat;
+}
+
+// ---- explicit assignments streamed through every requested set (include/pf_bytecode.h,
+// stream contract) ------------------------------------------------------------------------
+// Before a stream call's launches: the scratch words (queue heads, counter lines) to 0, and the
+// requested sets' first[] to "none" and count[] to 0 (count may be null).
+extern "C" __global__ void __launch_bounds__(256)
+pf_stream_reset_kernel(uint32_t* __restrict__ scratch, uint32_t n_scratch, uint32_t* __restrict__ first,
+                       uint32_t* __restrict__ count, uint32_t n_req) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_scratch + n_req; i += stride) {
+        if (i < n_scratch) {
+            scratch[i] = 0u;
+        } else {
+            first[i - n_scratch] = 0xFFFFFFFFu;
+            if (count) count[i - n_scratch] = 0u;
+        }
+    }
+}
+
+// Items (set, run of per_item consecutive 64-candidate groups) from the search's work queue, as a
+// census takes its groups.  A wave reads a group's assignments from the SoA rows of its set, runs
+// the program, and lane 0 stores the ballot of the roots, the group's verdict word; after the
+// item's last group it posts the item's smallest witness (one atomicMin, only if it has one) and
+// its popcount (one atomicAdd).  The host sizes per_item so that every wave takes a few dozen
+// items: one group per item left a light program (a compare over two variables) spending its
+// time on the claim and on the set's descriptor, 2.5 times the per-set launches' time.
+// order[k] is a requested set and pos[k] its place in the request: the outputs are in request
+// order.  first is never null (the host passes a block of its own when the caller wants none):
+// the one atomicMin that finds "none" in it is the set's first witness, which is how the sets
+// with a witness are counted (counter 4).
+template <int NREG>
+PF_INL void stream_body(const pf_set_desc* __restrict__ descs, const uint32_t* __restrict__ order,
+                        const uint32_t* __restrict__ pos, uint32_t n_sets, const uint4* __restrict__ code,
+                        const uint32_t* __restrict__ consts, const uint4* __restrict__ schema,
+                        const uint32_t* __restrict__ soa, uint32_t n_cand, uint32_t groups, uint32_t per_item,
+                        uint32_t flags, unsigned long long* __restrict__ bits, uint32_t* __restrict__ first,
+                        uint32_t* __restrict__ count, unsigned long long* __restrict__ counters,
+                        uint32_t* __restrict__ queue) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const uint32_t n_items = n_sets * ((groups + per_item - 1u) / per_item);
+    __shared__ uint2 pf_exp_lds[PF_SEARCH_LDS_U2];
+    uint2* exp_tbl = exp_tbl_of(pf_exp_lds);
+    UnitProf prof;
+#pragma unroll
+    for (int i = 0; i < PF_PROF_BUCKETS; i++) prof.c[i] = 0;
+    uint64_t evals_full = 0, decided = 0;
+    uint32_t n_sat = 0u;
+    for (uint32_t qi = 0; qi < PF_EARLY_QUEUES; ++qi) {
+        const uint32_t q = (wave + qi) % PF_EARLY_QUEUES;
+        const uint32_t nq = n_items > q ? (n_items - q + PF_EARLY_QUEUES - 1u) / PF_EARLY_QUEUES : 0u;
+        if (qi > 0u) {
+            uint32_t h = 0u;
+            if (lane == 0u) h = __hip_atomic_load(queue + q * PF_EARLY_QUEUE_STRIDE, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(h) >= nq) continue;
+        }
+        for (;;) {
+            uint32_t v = 0u;
+            if (lane == 0u) v = atomicAdd(queue + q * PF_EARLY_QUEUE_STRIDE, 1u);
+            const uint32_t k = __builtin_amdgcn_readfirstlane(v);
+            if (k >= nq) break;
+            const uint32_t item = k * PF_EARLY_QUEUES + q;
+            const uint32_t slot = item % n_sets, g0 = (item / n_sets) * per_item;
+            const uint32_t g1 = min(groups, g0 + per_item);
+            const uint32_t set = __builtin_amdgcn_readfirstlane(order[slot]);
+            const uint32_t req = __builtin_amdgcn_readfirstlane(pos[slot]);
+            const SetCtx S = make_ctx(descs, set, code, consts, schema, nullptr, 0ull);
+            // the set's rows of the SoA: variable v, limb l, candidate c at ((var_off + v) * 8 + l) * n_cand + c
+            const uint32_t* soa_s = soa + (size_t)__builtin_amdgcn_readfirstlane(descs[set].var_off) * 8u * n_cand;
+            uint32_t i_first = 0xFFFFFFFFu, i_count = 0u;  // of this item; wave-uniform
+            for (uint32_t group = g0; group < g1; ++group) {
+                const uint32_t cand = group * 64u + lane;
+                const bool active = cand < n_cand;
+                uint32_t complete = 0;
+                uint64_t lane_ops = 0;
+                const uint32_t sat = run_program<MODE_STREAM, NREG>(S, active ? cand : 0u, active, flags, soa_s, n_cand,
+                                                                 exp_tbl, &complete, &lane_ops, &prof);
+                const uint64_t m_act = pf::wave_mask(active);
+                const uint64_t m_sat = m_act & pf::wave_mask(sat != 0u);
+                decided += __popcll(m_act);
+                evals_full += __popcll(m_act & pf::wave_mask(complete != 0u));
+                if (bits && lane == 0u) bits[(size_t)req * groups + group] = (unsigned long long)m_sat;
+                // the groups of an item run in increasing order: its first witness is its smallest
+                if (m_sat && i_count == 0u) i_first = group * 64u + (uint32_t)__builtin_ctzll(m_sat);
+                i_count += (uint32_t)__popcll(m_sat);
+            }
+            if (lane == 0u && i_count) {
+                const uint32_t old = atomicMin(first + req, i_first);
+                n_sat += (uint32_t)(old == 0xFFFFFFFFu);
+                if (count) atomicAdd(count + req, i_count);
+            }
+        }
+    }
+    if (lane == 0) {
+        unsigned long long* cl = counters + PF_COUNTER_OFF / 8 + (wave % PF_COUNTER_STRIPES) * 16u;
+        if (evals_full) atomicAdd(cl + 0, (unsigned long long)evals_full);
+        if (decided) atomicAdd(cl + 1, (unsigned long long)decided);
+        if (n_sat) atomicAdd(cl + 4, (unsigned long long)n_sat);
+    }
+}
+
+#define PF_STREAM_PARAMS                                                                      \
+    const pf_set_desc *__restrict__ descs, const uint32_t *__restrict__ order,                 \
+        const uint32_t *__restrict__ pos, uint32_t n_sets, const uint4 *__restrict__ code,     \
+        const uint32_t *__restrict__ consts, const uint4 *__restrict__ schema,                 \
+        const uint32_t *__restrict__ soa, uint32_t n_cand, uint32_t groups, uint32_t per_item, \
+        uint32_t flags, unsigned long long *__restrict__ bits, uint32_t *__restrict__ first,   \
+        uint32_t *__restrict__ count, unsigned long long *__restrict__ counters,               \
+        uint32_t *__restrict__ queue
+#define PF_STREAM_ARGS                                                                        \
+    descs, order, pos, n_sets, code, consts, schema, soa, n_cand, groups, per_item, flags, bits, \
+        first, count, counters, queue
+
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_eval_stream_kernel(PF_STREAM_PARAMS) {
+    stream_body<PF_NW_NARROW + 1>(PF_STREAM_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_eval_stream_r16_kernel(PF_STREAM_PARAMS) {
+    stream_body<16>(PF_STREAM_ARGS);
 }
 
 // ---- materialise witness assignments --------------------------------------------------

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .ir import CLIMB_SCORE_SITES, CLIMB_WITNESS, LIMBS, Batch, Program, climb_score_id, from_limbs
+from .ir import CLIMB_SCORE_SITES, CLIMB_WITNESS, FLAG_SHORTCIRCUIT, LIMBS, Batch, Program, climb_score_id, from_limbs
 
 NOT_FOUND = 0xFFFFFFFF
 
@@ -71,6 +71,39 @@ class CensusResult:
     @property
     def sat(self) -> np.ndarray:
         return self.best_fails == 0
+
+
+@dataclass
+class StreamResult:
+    """Engine.eval_batch / eval_stream: one row per requested set, in request order
+    (include/pf_bytecode.h, stream contract).  eval_batch fills numpy arrays; eval_stream leaves
+    device tensors (bits as int64 words, first and count as int32 — reinterpret the bit patterns)
+    and no timing."""
+    bits: object             # [n, ceil(n_cand / 64)] uint64: bit c & 63 of word c >> 6 = candidate c
+    first: object            # [n] uint32 smallest satisfying candidate, or NOT_FOUND
+    count: object            # [n] uint32 satisfying candidates
+    n_cand: int
+    kernel_ms: float = 0.0
+    evals_full: int = 0
+    cands_decided: int = 0
+    n_sat: int = 0
+
+    def verdicts(self) -> np.ndarray:
+        """bits unpacked: bool [n, n_cand]."""
+        bits = self.bits
+        if not isinstance(bits, np.ndarray):     # a device tensor
+            bits = bits.cpu().numpy()
+        return unpack_bits(bits, self.n_cand)
+
+
+def unpack_bits(bits: np.ndarray, n_cand: int) -> np.ndarray:
+    """Verdict words [n, ceil(n_cand / 64)] (uint64, or the same bit patterns as int64) ->
+    bool [n, n_cand]."""
+    words = np.ascontiguousarray(bits).view(np.uint64).reshape(len(bits), -1)
+    if words.shape[1] != (n_cand + 63) // 64:
+        raise ValueError(f"{words.shape[1]} words per set for {n_cand} candidates")
+    by = words.astype("<u8", copy=False).view(np.uint8).reshape(len(words), -1)
+    return np.unpackbits(by, axis=1, bitorder="little")[:, :n_cand].astype(bool)
 
 
 class DeviceBatch:
@@ -369,6 +402,84 @@ class Engine:
             _lib.ptr_u32(descs), n_sets,
             _lib.ptr_u32(soa.reshape(-1) if soa.size else z), n_cand, _lib.ptr_u8(out)), "pf_eval_programs")
         return out[:n_sets * n_cand].reshape(n_sets, n_cand).astype(bool)
+
+    # ---- stream: explicit candidates through every set of a batch ---------------------------
+    @staticmethod
+    def _stream_request(db: DeviceBatch, shape, set_ids) -> np.ndarray:
+        """The request's set ids, after the checks the kernels cannot make: the SoA is
+        [V][8][n_cand] over the batch's V variables."""
+        n_vars = int(db.batch.schema.shape[0])
+        if len(shape) != 3 or shape[1] != LIMBS:
+            raise _lib.PathFeasError(f"stream: assignments of shape {tuple(shape)}, expected [V][{LIMBS}][n_cand]")
+        if shape[0] != n_vars:
+            raise _lib.PathFeasError(f"stream: {shape[0]} variable rows, the batch has {n_vars} "
+                                     "(ir.pack_soa lays them out)")
+        if shape[2] >= 1 << 32:
+            raise _lib.PathFeasError(f"stream: {shape[2]} candidates (at most 2^32 - 1)")
+        ids = range(len(db)) if set_ids is None else [int(s) & 0xFFFFFFFF for s in set_ids]
+        return np.ascontiguousarray(ids, dtype=np.uint32)
+
+    def eval_batch(self, db: DeviceBatch, soa: np.ndarray, set_ids: Optional[Sequence[int]] = None,
+                   shortcircuit: bool = True) -> StreamResult:
+        """Every explicit candidate of ``soa`` ([V][8][n_cand] uint32 over the batch's variables,
+        ir.pack_soa) against every requested set (default: all) in one call — pf_eval_batch;
+        include/pf_bytecode.h, stream contract."""
+        soa = np.asarray(soa)
+        if soa.dtype != np.uint32:
+            raise _lib.PathFeasError(f"stream: assignments of dtype {soa.dtype}, expected uint32")
+        ids = self._stream_request(db, soa.shape, set_ids)
+        soa = np.ascontiguousarray(soa)
+        n, n_cand = len(ids), int(soa.shape[2])
+        words = (n_cand + 63) // 64
+        bits = np.zeros((n, words), dtype=np.uint64)
+        first = np.full(n, NOT_FOUND, dtype=np.uint32)
+        count = np.zeros(n, dtype=np.uint32)
+        st = _lib.pf_stats()
+        _lib.check(_lib.lib().pf_eval_batch(
+            db.handle, _lib.ptr_u32(ids) if n else None, n, _lib.ptr_u32(soa.reshape(-1)) if soa.size else None,
+            n_cand, FLAG_SHORTCIRCUIT if shortcircuit else 0, _lib.ptr_u64(bits.reshape(-1)) if bits.size else None,
+            _lib.ptr_u32(first) if n else None, _lib.ptr_u32(count) if n else None, ctypes.byref(st)),
+            "pf_eval_batch")
+        return StreamResult(bits, first, count, n_cand, st.kernel_ms, st.evals_full, st.cands_decided, st.n_sat)
+
+    def eval_stream(self, db: DeviceBatch, soa_tensor, set_ids: Optional[Sequence[int]] = None, out=None,
+                    stream=None, shortcircuit: bool = True) -> StreamResult:
+        """eval_batch on device-resident candidates — pf_eval_batch_dev: ``soa_tensor`` is a
+        contiguous int32 / uint32 torch tensor [V][8][n_cand] on the batch's device, read through
+        its data_ptr() with no copy.  ``out``: a (bits, first, count) triple of device tensors to
+        write (int64 [n, words], int32 [n], int32 [n]; any of them None for "not wanted", not
+        all), default: new ones.  ``stream``: a torch stream (default: the current one).  Nothing
+        here waits for the device, except the first call with a given request: results are
+        ordered on the stream, which the caller synchronises."""
+        import torch
+
+        if not isinstance(soa_tensor, torch.Tensor) or not soa_tensor.is_cuda:
+            raise _lib.PathFeasError("stream: eval_stream takes a tensor on the GPU (eval_batch takes numpy)")
+        if soa_tensor.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise _lib.PathFeasError(f"stream: assignments of dtype {soa_tensor.dtype}, expected int32 / uint32")
+        if not soa_tensor.is_contiguous():
+            raise _lib.PathFeasError("stream: the assignments tensor is not contiguous")
+        ids = self._stream_request(db, tuple(soa_tensor.shape), set_ids)
+        n, n_cand = len(ids), int(soa_tensor.shape[2])
+        words = (n_cand + 63) // 64
+        dev = soa_tensor.device
+        if out is None:
+            out = (torch.empty((n, words), dtype=torch.int64, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        bits, first, count = out
+        for t, shape, dt, what in ((bits, (n, words), torch.int64, "bits"), (first, (n,), torch.int32, "first"),
+                                   (count, (n,), torch.int32, "count")):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise _lib.PathFeasError(f"stream: out {what} must be a contiguous {dt} tensor of shape {shape} "
+                                         f"on {dev}")
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        ptrs = [t.data_ptr() if t is not None else None for t in (bits, first, count)]
+        _lib.check(_lib.lib().pf_eval_batch_dev(
+            db.handle, _lib.ptr_u32(ids) if n else None, n, soa_tensor.data_ptr(), n_cand,
+            FLAG_SHORTCIRCUIT if shortcircuit else 0, *ptrs, None, s.cuda_stream), "pf_eval_batch_dev")
+        return StreamResult(bits, first, count, n_cand)
 
     # ---- keccak -------------------------------------------------------------------
     def keccak256(self, messages: Sequence[bytes]) -> List[bytes]:

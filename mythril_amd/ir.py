@@ -538,5 +538,30 @@ def pack_assignments_np(limbs: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.transpose(limbs, (1, 2, 0)))
 
 
+def pack_soa(batch: "Batch", assignments: Sequence[Optional[Sequence[Sequence[int]]]]) -> np.ndarray:
+    """Per-set explicit candidates -> the stream call's SoA limbs [V][8][n_cand] uint32 over
+    the batch's V variables (include/pf_bytecode.h, stream contract; pf_eval_programs' row
+    order): ``assignments[s]`` holds set s's candidates, each a list of its variables' values
+    in schema order, and fills rows ``descs[s].var_off ..``.  Every set given carries the same
+    number of candidates; a set given as None (one the call will not request) leaves its rows 0.
+    Values are taken mod 2^256: the kernels mask to each variable's width."""
+    if len(assignments) != len(batch):
+        raise ValueError(f"pack_soa: {len(assignments)} assignment lists for {len(batch)} sets")
+    counts = {len(a) for a in assignments if a is not None}
+    if len(counts) > 1:
+        raise ValueError(f"pack_soa: the sets carry different candidate counts {sorted(counts)}")
+    n = counts.pop() if counts else 0
+    out = np.zeros((int(batch.descs[:, 5].sum()) if len(batch) else 0, LIMBS, n), dtype=np.uint32)
+    for s, cands in enumerate(assignments):
+        off, nv = int(batch.descs[s][4]), int(batch.descs[s][5])
+        if cands is None or nv == 0 or n == 0:
+            continue
+        if any(len(c) != nv for c in cands):
+            raise ValueError(f"pack_soa: set {s} has {nv} variables")
+        flat = limbs_array([x for c in cands for x in c]).reshape(n, nv, LIMBS)
+        out[off:off + nv] = np.transpose(flat, (1, 2, 0))
+    return out
+
+
 def u32_bytes(words: Sequence[int]) -> bytes:
     return struct.pack(f"<{len(words)}I", *words)

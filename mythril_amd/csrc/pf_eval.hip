@@ -23,7 +23,8 @@ using pf::u256;
 // instruction's scalar fetch (10); slot = u64 index in the launch's counter scratch; bucket
 // PF_PROF_BUCKETS = whole-wave time
 #define PF_PROF_BUCKETS 18  // + DIV by udivrem256 path: 11 zero, 12 short, 13 one-digit, 14 general;
-                            // EXP parts: 15 window, 16 squarings, 17 Horner + product
+                            // EXP parts: 15 windowed b^e0 of waves without the series, 16 the
+                            // powering chain (squarings and b^e0's products), 17 Horner + product
 #define PF_PROF_SLOT 16
 
 // Register file: NREG wide registers (NREG - 1 usable + the write sink), limb-sliced into

@@ -643,30 +643,24 @@ PF_INL u256 exp256(const u256& base, const u256& e, uint32_t nbits, uint2* tbl, 
     return r;
 }
 
-// base^e for an exponent that fits one 32-bit word (the low part e0 of the 2-adic split):
-// the same windowed loop with the digits taken from that word — no 256-bit shifted exponent
-// live across the squarings (8 VGPRs fewer at the kernel's peak)
-// `want_b2` (wave-uniform): the caller reads base^2 back from entry 2 afterwards.
+// base^e for an exponent that fits one 32-bit word (the low part e0 of the 2-adic split, in
+// waves that do not run the series): the same windowed loop with the digits taken from that
+// word — no 256-bit shifted exponent live across the squarings (8 VGPRs fewer at the
+// kernel's peak)
 template <int WB = 2>
-PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, bool want_b2, uint2* tbl, uint32_t stride) {
+PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, uint2* tbl, uint32_t stride) {
     static_assert(WB == 2, "window");
     // The table holds base^1..base^3 in entries 1..3 (entry 0 is not the table's: the
     // narrow kernels keep a W register there, pf_eval.hip); digit 0 selects 1.  Only what is
     // read is built: with nbits <= 1 every lane's e is 0 or 1 and the result comes straight
-    // from registers, and base^2 is then formed only for the caller (exp256_split's series
-    // reads it from entry 2; base itself is dead across the loop).
+    // from registers.
     u256 one = zero256();
     one.l[0] = 1u;
-    const bool loop = nbits > 1u;
-    if (loop || want_b2) {
-        const u256 b2 = sqr256(base);
-        tbl_put(tbl, stride, 2u, b2);
-        if (loop) {
-            tbl_put(tbl, stride, 1u, base);
-            tbl_put(tbl, stride, 3u, mul256(b2, base));
-        }
-    }
-    if (!loop) return sel256((uint32_t)(e == 0u), one, base);
+    if (nbits <= 1u) return sel256((uint32_t)(e == 0u), one, base);
+    const u256 b2 = sqr256(base);
+    tbl_put(tbl, stride, 1u, base);
+    tbl_put(tbl, stride, 2u, b2);
+    tbl_put(tbl, stride, 3u, mul256(b2, base));
     const uint32_t nd = (nbits + WB - 1u) / WB;  // digits
     uint32_t d = (e >> (WB * (nd - 1u))) & 3u;
     u256 r = sel256((uint32_t)(d == 0u), one, tbl_get(tbl, stride, d));
@@ -699,12 +693,19 @@ PF_INL u256 exp256_w32(const u256& base, uint32_t e, uint32_t nbits, bool want_b
 // Level i lives mod 2^P_i, P_i = 256 - (valuation of d_1 ... d_{i-1}), on ceil(P_i / 32) limbs;
 // below 8 limbs its product is scanned by column with K_i as the accumulator's starting value
 // (tmul_add), at 8 limbs it is mul256 and one add256.
-// Neither t nor the per-level shift S_i is ever formed.  x = b^(2^M) - 1 mod 2^256 is b^2
-// squared M - 1 times (sqr256) less one, which is t_M mod 2^(254-M) — all of t_M that can
+// Neither t nor the per-level shift S_i is ever formed.  x = b^(2^M) - 1 mod 2^256 is b
+// squared M times (sqr256) less one, which is t_M mod 2^(254-M) — all of t_M that can
 // matter — already shifted by M + 2; the chain carries the factor as ((n - i + 1) t) << (M + 2),
 // a multiple of x that steps by x, and the levels' values scaled by the powers of two that
-// the factors are too large by (the scale schedule, below at exp_sched).  The windowed
-// left-to-right loop then runs over M exponent bits instead of 256.
+// the factors are too large by (the scale schedule, below at exp_sched).
+// b^e0 comes from the same squarings: they pass through b^2, b^4, ... b^(2^(M-1)), and
+//   b^e0 = prod_k (b^(2^k))^bit_k(e0),
+// taken right to left on that one chain, needs no squaring of its own — M squarings and at
+// most M - 1 products for the whole powering (8 + 7 at M = 8; a left-to-right 2-bit window
+// for b^e0 and a second climb for x were 14 + 4), and no table.  The product of step k is
+// skipped where no lane of the wave has bit k of e0.  Waves in which no lane runs the series
+// (every base even or every n = 0) keep the windowed left-to-right loop over e0's bits
+// (exp256_w32), as do splits whose e0 is wider than a word or whose window is 3 bits (exp256).
 // Even b: b^e = 0 for e >= 256 (2-adic valuation >= e), else e = e0 + 2^M n with n the
 // high part of a value < 256 — M >= 8 makes n = 0 and b^e = b^e0.
 // (tools/u256_fuzz.py checks this against Python's pow on the host build.)
@@ -930,8 +931,9 @@ PF_INL u256 horner(u256& G, const u256& T) {
         return tmul_add<L, LY, K.l[0], K.l[1], K.l[2], K.l[3], K.l[4], K.l[5], K.l[6]>(G, inner, K);
 }
 
-// pt (profiling builds, tools/unitprof.py): s_memtime cycles of the three parts —
-// windowed b^e0, the squarings up to b^(2^M), the Horner chain and final product
+// pt (profiling builds, tools/unitprof.py): s_memtime cycles of the three parts — the
+// windowed b^e0 of waves that run no series, the powering chain (the squarings up to b^(2^M)
+// with b^e0's products), the Horner chain and final product
 PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t stride,
                          uint64_t* pt = nullptr) {
 #if defined(PF_PROFILE_UNITS) && !defined(PF_HOST_MAC)
@@ -964,37 +966,53 @@ PF_INL u256 exp256_split(const u256& base, const u256& e, uint2* tbl, uint32_t s
     u256 n = shr256(e, (uint32_t)M, 0u);
 #pragma unroll
     for (int i = 0; i < 8; i++) n.l[i] = i < TL - 1 ? n.l[i] : (i == TL - 1 ? n.l[i] & TM : 0u);
-    // the series runs if some lane has an odd base and n != 0: known before the windowed part,
-    // which forms base^2 for it where its own table does not need one
+    // the series runs if some lane has an odd base and n != 0 (wave-uniform)
     const bool series = wave_any(wave_mask(odd != 0u) & ~wave_mask(iszero256(n) != 0u));
-    u256 r;
-    if constexpr (M <= 32 && WB == 2)
-        r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, series, tbl, stride);
-    else
-        r = exp256<WB>(base, e0, nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
-    PF_EXP_STAMP(0)
-    if (series) {
-        // b^e0 waits in the LDS table's entry 1 (base^1, no longer needed) while the
-        // squarings and the Horner chain run: 8 VGPRs fewer at their peak
-        tbl_put(tbl, stride, 1u, r);
-        // X = b^(2^M) - 1 = t_M << (M + 2) mod 2^256, the chain's step: b^2 (the window
-        // table's entry 2 where there is one) squared M - 1 times; b odd: no borrow
-        u256 X;
-        if constexpr (M <= 32 && WB == 2)
-            X = tbl_get(tbl, stride, 2u);
+    constexpr bool FUSED = M <= 32 && WB == 2;  // e0 is one word: its bits index at run time
+    u256 one = zero256();
+    one.l[0] = 1u;
+    u256 r, X;
+    if (FUSED && series) {
+        // One chain of squarings X = b^(2^k), k = 1 .. M, serves both parts: its last value
+        // less one is the series' step, and the values on the way are the factors of
+        // b^e0 = prod_k (b^(2^k))^bit_k(e0), taken right to left — b^e0 costs M - 1 products
+        // and no squaring or table of its own.  The lanes' bits are selects (lane_mask).
+        const uint32_t e0w = e0.l[0];
+        X = base;
+        r = sel256(e0w & 1u, base, one);
+#pragma unroll 1
+        for (uint32_t k = 1; k < (uint32_t)M; k++) {
+            X = sqr256(X);
+            // no lane has bit k (all of them from the wave's longest e0 on): nothing to
+            // multiply.  The test is wave-uniform, a scalar branch.
+            if (k >= nb0 || wave_none(wave_mask(((e0w >> k) & 1u) != 0u))) continue;
+            r = mul256(r, sel256((e0w >> k) & 1u, X, one));
+        }
+        X = sqr256(X);
+    } else {
+        if constexpr (FUSED)
+            r = exp256_w32<WB>(base, e0.l[0], nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
         else
+            r = exp256<WB>(base, e0, nb0 < (uint32_t)M ? nb0 : (uint32_t)M, tbl, stride);
+        PF_EXP_STAMP(0)
+        if (series) {  // a multi-limb e0 or a 3-bit window: the step by its own squarings
             X = sqr256(base);
 #pragma unroll 1
-        for (int k = 1; k < M; k++) X = sqr256(X);
+            for (int k = 1; k < M; k++) X = sqr256(X);
+        }
+    }
+    if (series) {
+        // X = b^(2^M) - 1 = t_M << (M + 2) mod 2^256, the chain's step; b odd: no borrow
         X.l[0] -= 1u;
+        // b^e0 waits in the LDS table's entry 1 while the Horner chain runs: 8 VGPRs fewer
+        // at its peak
+        tbl_put(tbl, stride, 1u, r);
         PF_EXP_STAMP(1)
         // the chain's innermost factor G_J = (n - J + 1) X: one borrow chain (mod 2^256: the
         // product is the same) and one product
         u256 G = mul256(sub_small256(n, (uint32_t)(J - 1)), X);
         u256 h = horner<M, 1, J>(G, X);
-        u256 one = zero256();  // even base: n != 0 means e >= 256 -> result 0 below
-        one.l[0] = 1u;
-        h = sel256(odd, h, one);
+        h = sel256(odd, h, one);  // even base: n != 0 means e >= 256 -> result 0 below
         r = mul256(tbl_get(tbl, stride, 1u), h);
         PF_EXP_STAMP(2)
     }

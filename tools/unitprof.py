@@ -20,7 +20,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PROF_SO = os.path.join(ROOT, "mythril_amd", "libpathfeas_prof.so")
 BUCKETS = ["ALU", "MUL", "DIV", "SHIFT", "GEN", "CMP", "BOOL", "END", "EXP", "CONST", "FETCH",
-           "DIV_zero", "DIV_short", "DIV_onedigit", "DIV_general", "EXP_window", "EXP_t", "EXP_horner"]
+           "DIV_zero", "DIV_short", "DIV_onedigit", "DIV_general",
+           # EXP's parts: the windowed b^e0 of waves that run no series, the powering chain (the
+           # squarings up to b^(2^M) with b^e0's products), the Horner chain and final product
+           "EXP_window_noseries", "EXP_chain", "EXP_horner"]
 
 
 def build():
@@ -35,7 +38,7 @@ def build():
 def run(args):
     from mythril_amd import _lib, ir, synth
 
-    L = _lib.load_library(PROF_SO)
+    L = _lib.load_library(args.lib or PROF_SO)
     L.pf_prof_read.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     L.pf_prof_read.restype = ctypes.c_int
     from mythril_amd.engine import Engine
@@ -65,5 +68,6 @@ if __name__ == "__main__":
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--sets", type=int, default=512)
     ap.add_argument("--budget", type=int, default=65536)
+    ap.add_argument("--lib", default=None, help="another profiling build (a parent's, for an A/B)")
     a = ap.parse_args()
     build() if a.build else run(a)

@@ -308,83 +308,114 @@ def _place(others, special, pos):
     return lanes
 
 
-def wave(name, pos):
-    """The 64 (a, b) lanes of a wave with its special lane at ``pos``, checked against the
-    model for what the wave is there for."""
+def wave_parts(name, nl=8):
+    """(the 63 other lanes, the special lane) of a wave over operands of ``nl`` limbs: 8, or 6 —
+    below 2^192, non-negative at width 256, so the signed ops hand the divider these very
+    operands under every combination of signs."""
     rng = _rng(100 + WAVES.index(name))
-    top = 1 << 256
+    top = 1 << (32 * nl)
+    half = nl // 2
     if name == "bz_in_general":
-        others = [(_rand(rng, 8), _rand(rng, 2 + i % 4)) for i in range(63)]
-        lanes = _place(others, (_rand(rng, 8), 0), pos)
-        assert wave_path(lanes) == "general"
-        assert all(t["skip"] for t in general_trace(*lanes[pos]))
+        others = [(_rand(rng, nl), _rand(rng, 2 + i % 4)) for i in range(63)]
+        special = (_rand(rng, nl), 0)
     elif name == "lone_high_digit":
-        # the others' divisors have four limbs: their digits 7..5 are 0; the special lane's
-        # one-limb divisor is below its a's top limb: digit 7
-        others = [(_rand(rng, 8), _rand(rng, 4)) for i in range(63)]
-        lanes = _place(others, (_rand(rng, 8, top=0xF0000000), 0x10001), pos)
-        assert wave_path(lanes) == "general"
-        digs = wave_digits(lanes)
-        assert max(digs) == 7 and digs[7][0] == [pos] and digs[6][0] == [pos] and digs[5][0] == [pos]
+        # the others' divisors fill half the limbs: their highest digits are 0; the special
+        # lane's one-limb divisor is below its a's top limb: digit nl - 1
+        others = [(_rand(rng, nl), _rand(rng, half)) for i in range(63)]
+        special = (_rand(rng, nl, top=0xF0000000), 0x10001)
     elif name == "lone_low_digit":
         # the others: a = b (Q << 32) + r with r < b / 2: digit 0 estimates below 1
         others = []
         for i in range(63):
-            b = _rand(rng, 3)
-            others.append((b * (_rand(rng, 3) << 32) + b // (2 + i), b))
-        b = _rand(rng, 3)
-        lanes = _place(others, (b * ((_rand(rng, 3) << 32) + 0x1234567) + 99, b), pos)
-        assert wave_path(lanes) == "general"
-        digs = wave_digits(lanes)
-        assert min(digs) == 0 and digs[0][0] == [pos] and len(digs[1][0]) == 64
+            b = _rand(rng, half - 1)
+            others.append((b * (_rand(rng, half - 1) << 32) + b // (2 + i), b))
+        b = _rand(rng, half - 1)
+        special = (b * ((_rand(rng, half - 1) << 32) + 0x1234567) + 99, b)
     elif name == "lone_addback_onedigit":
         others = []
         for i in range(63):
-            b = _rand(rng, 2 + i % 6)
+            b = _rand(rng, 2 + i % (nl - 2))
             others.append((b * int(rng.integers(1, B32 - 3)) + b // (2 + i), b))
-        b = _rand(rng, 5)
-        lanes = _place(others, (b * 0xFEDCBA98 + (b - 1), b), pos)
-        assert wave_path(lanes) == "onedigit"
-        assert [i for i, l in enumerate(lanes) if onedigit_trace(*l)[2]] == [pos]
+        b = _rand(rng, nl - 3)
+        special = (b * 0xFEDCBA98 + (b - 1), b)
     elif name == "lone_addback_general":
-        others = [(_rand(rng, 8), _rand(rng, 2 + i % 4)) for i in range(63)]
-        b = _rand(rng, 3)
-        lanes = _place(others, (b * from_digits([0x31415926, 0x53589793, 0x23846264, 0x33832795]) + (b - 1), b), pos)
-        assert wave_path(lanes) == "general"
-        digs = wave_digits(lanes)
-        assert sorted({i for _, fix in digs.values() for i in fix}) == [pos] and digs[0][1] == [pos]
+        others = [(_rand(rng, nl), _rand(rng, 2 + i % 4)) for i in range(63)]
+        b = _rand(rng, half - 1)
+        special = (b * from_digits([0x31415926, 0x53589793, 0x23846264, 0x33832795]) + (b - 1), b)
     elif name == "bhigh_next_to_one_limb":
-        # full-length divisors (b * 2^32j passes nine limbs from j = 2 on) whose lanes must sit
-        # out the digits 7..2 that the one-limb lanes execute; the special lane is a one-limb one
-        # among 32 of each
-        others = [(_rand(rng, 8, top=0xFFFFFFF0 | i % 16), _rand(rng, 8, top=1 + i % 3)) if i % 2 else
-                  (_rand(rng, 8), _rand(rng, 1)) for i in range(63)]
-        lanes = _place(others, (top - 1, 3), pos)
-        assert wave_path(lanes) == "general"
-        tr = [general_trace(a, b) for a, b in lanes]
-        long = [i for i, (a, b) in enumerate(lanes) if limbs(b) == 8]
-        assert len(long) >= 31 and all(tr[i][k]["skip"] for i in long for k in range(6))
-        assert all(not tr[i][6]["skip"] and tr[i][7]["want"] for i in long)
-        assert sorted(wave_digits(lanes)) == list(range(8))
+        # full-length divisors (b * 2^32j passes nine limbs from j = 10 - nl on) whose lanes must
+        # sit out the digits that the one-limb lanes execute above that; the special lane is a
+        # one-limb one among 32 of each
+        others = [(_rand(rng, nl, top=0xFFFFFFF0 | i % 16), _rand(rng, nl, top=1 + i % 3)) if i % 2 else
+                  (_rand(rng, nl), _rand(rng, 1)) for i in range(63)]
+        special = (top - 1, 3)
     elif name == "zeros_and_one_general":
         others = []
         for i in range(63):
-            b = _rand(rng, 1 + i % 8)
-            others.append((0, 0) if i == 7 else (_rand(rng, 8), 0) if i % 9 == 0 else (max(b - 1 - i, 0), b))
-        lanes = _place(others, (_rand(rng, 8), _rand(rng, 3)), pos)
-        assert wave_path(lanes) == "general"
-        assert [i for i, l in enumerate(lanes) if not lane_zero(*l)] == [pos]
+            b = _rand(rng, 1 + i % nl)
+            others.append((0, 0) if i == 7 else (_rand(rng, nl), 0) if i % 9 == 0 else (max(b - 1 - i, 0), b))
+        special = (_rand(rng, nl), _rand(rng, 3))
     elif name == "q0_in_onedigit":
         # the quotient 0 on the one-digit path: one a < b lane among one-digit lanes
         others = []
         for i in range(63):
-            b = _rand(rng, 2 + i % 6)
+            b = _rand(rng, 2 + i % (nl - 2))
             others.append((b * int(rng.integers(1, B32 - 3)) + b // (3 + i), b))
-        b = _rand(rng, 6)
-        lanes = _place(others, (b - 1, b), pos)
+        b = _rand(rng, nl - 2)
+        special = (b - 1, b)
+    else:
+        raise ValueError(name)
+    return others, special
+
+
+def check_wave(name, lanes, pos, nl=8):
+    """Asserts, against the model, what the wave ``name`` is there for: ``lanes`` are 64 (a, b)
+    pairs as the divider sees them, the special lane at ``pos`` — the others in any order and
+    with repeats (tests/lane_table_cases.py draws them from a table)."""
+    assert len(lanes) == 64
+    top = 1 << (32 * nl)
+    if name == "bz_in_general":
+        assert wave_path(lanes) == "general"
+        assert all(t["skip"] for t in general_trace(*lanes[pos]))
+    elif name == "lone_high_digit":
+        assert wave_path(lanes) == "general"
+        digs = wave_digits(lanes)
+        assert max(digs) == nl - 1 and all(digs[j][0] == [pos] for j in range(nl - 1, nl // 2, -1))
+    elif name == "lone_low_digit":
+        assert wave_path(lanes) == "general"
+        digs = wave_digits(lanes)
+        assert min(digs) == 0 and digs[0][0] == [pos] and len(digs[1][0]) == 64
+    elif name == "lone_addback_onedigit":
+        assert wave_path(lanes) == "onedigit"
+        assert [i for i, l in enumerate(lanes) if onedigit_trace(*l)[2]] == [pos]
+    elif name == "lone_addback_general":
+        assert wave_path(lanes) == "general"
+        digs = wave_digits(lanes)
+        assert sorted({i for _, fix in digs.values() for i in fix}) == [pos] and digs[0][1] == [pos]
+    elif name == "bhigh_next_to_one_limb":
+        assert wave_path(lanes) == "general"
+        tr = [general_trace(a, b) for a, b in lanes]
+        long = [i for i, (a, b) in enumerate(lanes) if limbs(b) == nl]
+        assert len(long) >= 31 and all(tr[i][k]["skip"] for i in long for k in range(nl - 2))
+        assert all(not tr[i][6]["skip"] and tr[i][7]["want"] for i in long)
+        assert sorted(wave_digits(lanes)) == list(range(nl))
+        assert limbs(lanes[pos][1]) == 1
+    elif name == "zeros_and_one_general":
+        assert wave_path(lanes) == "general"
+        assert [i for i, l in enumerate(lanes) if not lane_zero(*l)] == [pos]
+    elif name == "q0_in_onedigit":
         assert wave_path(lanes) == "onedigit"
         assert onedigit_trace(*lanes[pos]) == (0, False, True)   # fraction (b - 1) / b: add-back to 0
+        assert [i for i, (a, b) in enumerate(lanes) if a < b] == [pos]
     else:
         raise ValueError(name)
     assert all(0 <= a < top and 0 <= b < top for a, b in lanes)
+
+
+def wave(name, pos, nl=8):
+    """The 64 (a, b) lanes of a wave with its special lane at ``pos``, checked against the
+    model for what the wave is there for."""
+    others, special = wave_parts(name, nl)
+    lanes = _place(others, special, pos)
+    check_wave(name, lanes, pos, nl)
     return lanes

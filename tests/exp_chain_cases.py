@@ -166,3 +166,49 @@ def wave_all_n0(w, seed=0xE):
 def _cut(lanes, w):
     mask = (1 << w) - 1
     return [(b & mask, e & mask) for b, e in lanes]
+
+
+# ---- what each wave is there for: predicates over 64 (base, exponent) lanes ----------------
+
+def _e0s(lanes):
+    return [split_e(e)[0] for _, e in lanes]
+
+
+def is_mixed(lanes):
+    odd_n0 = [b & 1 and split_e(e)[1] == 0 for b, e in lanes]
+    n_odd = sum(b & 1 for b, _ in lanes)
+    return (runs_series(lanes) and n_odd == 32 and 3 * sum(odd_n0) >= n_odd
+            and {e0 for (b, _), e0 in zip(lanes, _e0s(lanes)) if b & 1} >= set(PATTERNS))
+
+
+def has_bits_clear(lanes):
+    e0s = _e0s(lanes)
+    seen = 0
+    for e0 in e0s:
+        seen |= e0
+    return runs_series(lanes) and seen == 0xFF & ~0x48 and all(split_e(e)[1] for _, e in lanes)
+
+
+def is_short(lanes):
+    return (runs_series(lanes) and max(e0.bit_length() for e0 in _e0s(lanes)) == 3
+            and set(_e0s(lanes)) == set(range(8)) and all(split_e(e)[1] for _, e in lanes))
+
+
+def all_even(lanes):
+    return (not runs_series(lanes) and not any(b & 1 for b, _ in lanes)
+            and {e >= 256 for _, e in lanes} == {False, True})
+
+
+def all_n0(lanes):
+    return (not runs_series(lanes) and all(e < 256 for _, e in lanes)
+            and {b & 1 for b, _ in lanes} == {0, 1}
+            and {e.bit_length() for _, e in lanes} >= {0, 1, 8})
+
+
+WAVES = {
+    "mixed": (wave_mixed, is_mixed),
+    "bits_3_6_clear": (wave_bits_clear, has_bits_clear),
+    "short_e0": (wave_short_e0, is_short),
+    "no_series_even": (wave_all_even, all_even),
+    "no_series_n0": (wave_all_n0, all_n0),
+}

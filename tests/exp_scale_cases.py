@@ -90,3 +90,29 @@ def pairs(m, nrandom_bases, seed=0x5CA1E):
     rng = random.Random(seed + m)
     ns = sorted({n for lv in unscaling_levels(m) for n in (lv - 1, lv, lv + 1)} | {(1 << 246) - 1})
     return [(b, (e0 + (n << m)) & MASK) for b in bases(m, rng, nrandom_bases) for n in ns for e0 in (0, 255)]
+
+
+def mixed_wave(w, m=8):
+    """One wave of 64 (base, exponent) lanes at width w: odd and even bases alternate, n walks
+    over the un-scaling levels and their neighbours (and 0 and 2^246 - 1), t all ones / 1 /
+    random rotate."""
+    import numpy as np
+
+    rng = np.random.default_rng(0x5CA1E + w)
+    Mw = (1 << w) - 1
+    ones, tiny = bases(m, None, 0)
+    ns = sorted({n for lv in unscaling_levels(m) for n in (lv - 1, lv, lv + 1)} | {(1 << 246) - 1})
+    assert ns[0] == 0
+    lanes = []
+    for lane in range(64):
+        b = (ones, tiny, int.from_bytes(rng.bytes(32), "little") | 1)[lane % 3]
+        if lane % 4 == 3:
+            b &= ~1
+        n = ns[lane % len(ns)]
+        lanes.append((b & Mw, ((0, 255)[(lane >> 2) & 1] + (n << m)) & Mw))
+    return lanes
+
+
+def is_mixed_wave(lanes):
+    """Odd and even bases, each with exponents below and from 256 on."""
+    return {(b & 1, e >= 256) for b, e in lanes} == {(0, False), (0, True), (1, False), (1, True)}

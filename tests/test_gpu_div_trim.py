@@ -10,7 +10,9 @@ against oracle/pyoracle.py, bit-exact.
   and digits 0 under an estimate of 1, at the highest and lowest executed digit).
 * Mixed waves of 64 lanes through ``eval_assignments`` (the SoA kernel), where the scalar mask
   combinations can go wrong: one lane differs from the other 63 in the one condition a test is
-  about, and sits at lane 0, 31, 32 or 63 — both halves of the 64-bit mask.
+  about, and sits at lane 0, 31, 32 or 63 — both halves of the 64-bit mask.  The same waves
+  reach the search, stream, census and climb kernels, under all five ops, in
+  tests/test_gpu_mixed_waves.py (the lane-table protocol of lane_table_cases.py).
 
 div_trim_cases.py builds the operands and asserts, with a model of the divider in Python
 integers, that each reaches its path and digits; tests/test_div_trim_cases.py runs the same

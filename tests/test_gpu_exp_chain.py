@@ -8,7 +8,9 @@ single-bit and alternating patterns of e0 under n in {0, 1, 2^246 - 1}, bases 0,
 protocol of op_programs.py: both register files, the full sweep and the early-exit kernels,
 widths 256 and 200, every row as a set that holds and as one whose expectation is wrong in one
 bit.  A candidate-0 wave is uniform, so the waves in which lanes differ go through
-``eval_assignments`` (the SoA kernel), 64 lanes each:
+``eval_assignments`` (the SoA kernel) here, 64 lanes each, and through the search, stream, census
+and climb kernels in tests/test_gpu_mixed_waves.py (the lane-table protocol of
+lane_table_cases.py):
  (a) odd and even bases alternate, e0 walks the patterns, n = 0 in a third of the odd lanes —
      the series runs for the wave while those lanes need (1 + X)^0 = 1;
  (b) bits 3 and 6 of e0 clear in every lane — the products of those steps are skipped;
@@ -49,48 +51,7 @@ def test_exp_chain_rows_through_search(engine, w, base, flags):
     _run(engine, rows, base, flags)
 
 
-def _e0s(lanes):
-    return [C.split_e(e)[0] for _, e in lanes]
-
-
-def _is_mixed(lanes):
-    odd_n0 = [b & 1 and C.split_e(e)[1] == 0 for b, e in lanes]
-    n_odd = sum(b & 1 for b, _ in lanes)
-    return (C.runs_series(lanes) and n_odd == 32 and 3 * sum(odd_n0) >= n_odd
-            and {e0 for (b, _), e0 in zip(lanes, _e0s(lanes)) if b & 1} >= set(C.PATTERNS))
-
-
-def _has_bits_clear(lanes):
-    e0s = _e0s(lanes)
-    seen = 0
-    for e0 in e0s:
-        seen |= e0
-    return C.runs_series(lanes) and seen == 0xFF & ~0x48 and all(C.split_e(e)[1] for _, e in lanes)
-
-
-def _is_short(lanes):
-    return (C.runs_series(lanes) and max(e0.bit_length() for e0 in _e0s(lanes)) == 3
-            and set(_e0s(lanes)) == set(range(8)) and all(C.split_e(e)[1] for _, e in lanes))
-
-
-def _all_even(lanes):
-    return (not C.runs_series(lanes) and not any(b & 1 for b, _ in lanes)
-            and {e >= 256 for _, e in lanes} == {False, True})
-
-
-def _all_n0(lanes):
-    return (not C.runs_series(lanes) and all(e < 256 for _, e in lanes)
-            and {b & 1 for b, _ in lanes} == {0, 1}
-            and {e.bit_length() for _, e in lanes} >= {0, 1, 8})
-
-
-WAVES = {
-    "mixed": (C.wave_mixed, _is_mixed),
-    "bits_3_6_clear": (C.wave_bits_clear, _has_bits_clear),
-    "short_e0": (C.wave_short_e0, _is_short),
-    "no_series_even": (C.wave_all_even, _all_even),
-    "no_series_n0": (C.wave_all_n0, _all_n0),
-}
+WAVES = C.WAVES      # the waves and the predicates that say what each is there for
 
 
 @pytest.mark.parametrize("w", [256, 200])

@@ -8,8 +8,9 @@ that level is the last that matters) and at 2^246 - 1, under bases whose t is al
 random, e0 in {0, 255}; a few random pairs follow.  Rows reach the search kernels by the
 candidate-0 protocol of op_programs.py: both register files, the full sweep and the early-exit
 kernels, widths 256 and 200, every row as a set that holds and as one whose expectation is wrong
-in one bit.  One mixed wave goes through ``eval_assignments`` (the SoA kernel): odd and even
-bases side by side, n at and around the un-scaling levels."""
+in one bit.  One mixed wave (exp_scale_cases.mixed_wave) goes through ``eval_assignments`` (the
+SoA kernel): odd and even bases side by side, n at and around the un-scaling levels; the other
+kernels get it in tests/test_gpu_mixed_waves.py."""
 
 import functools
 
@@ -60,20 +61,10 @@ def test_exp_scale_rows_through_search(engine, w, base, flags):
 def test_exp_scale_mixed_wave(engine, w):
     """One wave of 64 lanes: odd and even bases alternate, n walks over the un-scaling levels
     and their neighbours (and 0 and 2^246 - 1), t all ones / 1 / random rotate."""
-    rng = np.random.default_rng(0x5CA1E + w)
-    Mw = ir.mask(w)
     prog = _op_program("exp", w)
     db = engine.upload([prog])
-    ones, tiny = S.bases(SPLIT, None, 0)
-    ns = sorted({n for lv in S.unscaling_levels(SPLIT) for n in (lv - 1, lv, lv + 1)} | {(1 << 246) - 1})
-    assert ns[0] == 0
     cands, wrong = [], []
-    for lane in range(64):
-        b = (ones, tiny, int.from_bytes(rng.bytes(32), "little") | 1)[lane % 3]
-        if lane % 4 == 3:
-            b &= ~1
-        n = ns[lane % len(ns)]
-        b, e = b & Mw, ((0, 255)[(lane >> 2) & 1] + (n << SPLIT)) & Mw
+    for lane, (b, e) in enumerate(S.mixed_wave(w, SPLIT)):
         r = O.bvexp(b, e, w)
         assert r == pow(b, e, 1 << w)
         cands.append([b, e, r])

@@ -9,12 +9,14 @@ tests/test_exp_series_host.py reduced to a few hundred rows.
 Rows reach the search kernels by the candidate-0 protocol of op_programs.py, as the EXP grid of
 test_gpu_narrow_ops.py does: both register files, the full sweep and the early-exit kernels,
 widths 256 and 200, every row as a set that holds and as one whose expectation is wrong in one
-bit.  One mixed wave goes through ``eval_assignments`` (the SoA kernel): 64 lanes with odd and
-even bases and n = 0 and n != 0 side by side, so the series runs under a wave-uniform branch
-that only some lanes need."""
+bit.  One mixed wave (exp_series_cases.mixed_wave) goes through ``eval_assignments`` (the SoA
+kernel): 64 lanes with odd and even bases and n = 0 and n != 0 side by side, so the series runs
+under a wave-uniform branch that only some lanes need; the other kernels get it in
+tests/test_gpu_mixed_waves.py."""
 
 import functools
 
+import exp_series_cases as X
 import numpy as np
 import op_programs as P
 import pyoracle as O
@@ -85,19 +87,10 @@ def test_exp_series_grid_through_search(engine, w, base, flags):
 def test_exp_series_mixed_wave(engine, w):
     """One wave of 64 lanes: odd / even bases alternate, and so do n = 0 and n != 0, so every
     combination sits next to the others while the series runs for the lanes that need it."""
-    rng = np.random.default_rng(0x3A7E + w)
-    Mw = ir.mask(w)
     prog = _op_program("exp", w)
     db = engine.upload([prog])
     cands, wrong = [], []
-    for lane in range(64):
-        b = int.from_bytes(rng.bytes(32), "little")
-        b = (b | 1) if lane & 1 else (b & ~1)
-        if lane % 8 == 7:
-            b = ((1 << (8 + lane)) + 1) & Mw           # t tiny
-        e0 = int(rng.integers(0, 256))
-        n = 0 if lane & 2 else [1, 2, lane, 1 << lane, int.from_bytes(rng.bytes(31), "little")][lane % 5]
-        b, e = b & Mw, (e0 + 256 * n) & Mw
+    for lane, (b, e) in enumerate(X.mixed_wave(w)):
         r = O.bvexp(b, e, w)
         assert r == pow(b, e, 1 << w)
         cands.append([b, e, r])

@@ -10,7 +10,9 @@ Python integers and oracle/pyoracle.py, bit-exact.
   odd and even bases under exponents 0, 1, 2, 3, 255, 256, 256 n (+ 1, 2, 3), 2^84, 2^254,
   2^256 - 1: the series with nb0 = 0, 1, >= 2 and no series with nb0 = 0, 1, 2, 8.
 * Mixed waves of 64 lanes through ``eval_assignments`` (the SoA kernel): 63 lanes of one of
-  those classes and one lane of another, at lane 0, 31, 32 or 63.
+  those classes and one lane of another, at lane 0, 31, 32 or 63.  The same waves, and a MUL wave
+  of carrying and non-carrying columns, reach the search, stream, census and climb kernels in
+  tests/test_gpu_mixed_waves.py (the lane-table protocol of lane_table_cases.py).
 
 products_cases.py builds the operands and asserts what they are for; tests/test_products_host.py
 runs the same rows through the host mirrors."""

@@ -123,6 +123,22 @@ int pf_check_batches(const uint64_t* handles, size_t n, uint64_t global_seed, ui
 int pf_check_batch_dev(uint64_t handle, uint64_t global_seed, uint32_t budget, uint32_t flags,
                        uint32_t timeout_ms, uint32_t* d_found, pf_stats* stats, void* stream);
 
+/* Linked search (include/pf_bytecode.h, link contract): group_of[s] in [0, n_groups) is set s's
+ * link group, every set in exactly one; found_out[g] = the smallest candidate in [0, budget) at
+ * which every member of group g holds, or 0xFFFFFFFF.  flags as for pf_check_batch (none changes
+ * a verdict).  stats: n_sat = groups with a witness, timed_out as for pf_check_batch (a cut
+ * call's witnesses are still witnesses), kernel_ms over all of the call's launches, evals_full
+ * and cands_decided = the lanes that were run (with early exit not promised to repeat from run
+ * to run).  An id out of range, an empty group, a group of more than PF_LINK_MAX_PARTS sets,
+ * members that differ in what the contract says they share, budget == 0: error, nothing
+ * launched, nothing written.  The per-call state (verdicts, and 12 B per group and 64
+ * candidates) lives in the batch's link block, allocated by its first linked call and grown by
+ * a later one that needs more; pf_check_batch's found[] and every other call on the batch are
+ * untouched by it.  pf_materialize of any member at found_out[g] is the group's assignment.  */
+int pf_check_linked(uint64_t handle, uint64_t global_seed, uint32_t budget, uint32_t flags,
+                    uint32_t timeout_ms, const uint32_t* group_of, uint32_t n_groups,
+                    uint32_t* found_out, pf_stats* stats);
+
 /* Regenerate the full assignment of candidate cand_ids[i] of set set_ids[i]: writes
  * n_vars(set) x 8 u32 per request, concatenated in request order.                        */
 int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_ids,

@@ -431,6 +431,43 @@ enum pf_census_status {
  * nothing is launched; n == 0 or n_cand == 0 (with valid ids and flags) returns 0, launches
  * nothing and writes no output, whatever the output pointers are.                          */
 
+/* ---- link contract -------------------------------------------------------------- */
+/* A linked search (pf_check_linked) finds the smallest candidate at which several programs hold
+ * at once.  Candidates are never stored: candidate c of variable v is a function of the global
+ * seed, the set seed, c, v, the schema entry, the constant pool and the parents (generator
+ * contract above), so programs that share all of those see one candidate stream, each generating
+ * only the variables it reads.  A long conjunction split into K programs over disjoint groups of
+ * its roots (lower_parts) is so searched by K waves per 64 candidates instead of one.
+ *
+ * A link group is a non-empty list of sets of one batch, at most PF_LINK_MAX_PARTS of them.  Its
+ * members agree in
+ *    n_vars, and per variable the schema words 0 .. 2 (kind | width << 8, hint0, hint1);
+ *    n_const and the first n_const constants of each member's range — the caller's pool; the
+ *       constants the fold pass gives a device program of its own come after them, are never
+ *       drawn by the generator and do not count;
+ *    seed;
+ *    parents: per variable, either no member has a parent value or all have the same one (schema
+ *       word 3 is a slot in the batch's parent array and is compared by the value it names).
+ * Candidate c is a witness of the group iff the root of every member's device program holds
+ * under it.  The group's verdict is the smallest such c in [0, budget), or 0xFFFFFFFF.  A group
+ * of one set has exactly that set's pf_check_batch verdict under the same (global seed, budget).
+ *
+ * Flags.  PF_FLAG_SHORTCIRCUIT, PF_FLAG_EARLY_EXIT and PF_FLAG_NO_PROBE keep their meaning and
+ * none changes a verdict: with early exit a wave leaves a range of candidates only once the
+ * group's verdict is at or below the range's next candidate — a member that holds somewhere says
+ * nothing about the others, so its own hit ends nothing.  PF_FLAG_COUNT_OPS: ops counts the
+ * lanes that were executed (a wave may skip 64 candidates that an earlier member already failed
+ * as a whole, so the count, like evals_full and cands_decided, depends on the order of arrival).
+ *
+ * PF_LINK_MAX_PARTS.  Every part pays a fixed price per 64 candidates that its length does not
+ * shrink: the generator for the variables it reads, subterms it shares with other parts emitted
+ * again, and its two device-scope atomics (mask, arrival count).  The longest programs this
+ * engine meets are about 2,000 instructions; at 64 parts such a program's share
+ * is some 30 instructions, the size of that fixed price, so a finer split cannot shorten the
+ * walk, and a caller asking for more has made a mistake worth reporting.  The arrival count is
+ * a u32 and would take any number.                                                          */
+#define PF_LINK_MAX_PARTS 64u
+
 /* flags for pf_check_batch */
 #define PF_FLAG_SHORTCIRCUIT 1u  /* stop a wave's set evaluation once all its lanes are false */
 #define PF_FLAG_EARLY_EXIT 2u    /* stop a set once any candidate satisfies it             */

@@ -56,6 +56,9 @@ SIGNATURES = {
     "pf_check_batch": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                       ctypes.c_uint32, ctypes.c_uint32, _u32p, _u8p,
                                       ctypes.POINTER(pf_stats)]),
+    "pf_check_linked": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p,
+                                       ctypes.POINTER(pf_stats)]),
     "pf_check_batches": (ctypes.c_int, [_u64p, _sz, ctypes.c_uint64, ctypes.c_uint32,
                                         ctypes.c_uint32, ctypes.c_uint32, _u32p,
                                         ctypes.POINTER(pf_stats)]),

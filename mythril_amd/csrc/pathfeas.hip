@@ -153,11 +153,20 @@ struct Batch {
     void* e_mem = nullptr;
     size_t e_cap = 0;
     std::vector<uint32_t> e_req;
+    // linked search (pf_check_linked): host copies of what a link group's members share, and
+    // the link block — this call's group of every set and members of every group, the groups'
+    // verdicts, one (mask, count) record per group and 64 candidates — allocated by the batch's
+    // first linked call, grown when a later call needs more; l_req is the group_of it holds
+    LinkTables h_link;
+    void* l_mem = nullptr;
+    size_t l_cap = 0;
+    std::vector<uint32_t> l_req;
     ~Batch() {  // the device block goes back to its device's pool first (release_batch)
         if (d_mem) hipFree(d_mem);
         if (c_mem) hipFree(c_mem);
         if (s_mem) hipFree(s_mem);
         if (e_mem) hipFree(e_mem);
+        if (l_mem) hipFree(l_mem);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
     }
@@ -231,6 +240,10 @@ void release_batch(Dev* D, Batch* B) {
     if (D && B->e_mem) {
         pool_release(D, B->e_mem, B->e_cap);
         B->e_mem = nullptr;
+    }
+    if (D && B->l_mem) {
+        pool_release(D, B->l_mem, B->l_cap);
+        B->l_mem = nullptr;
     }
     if (D) {
         std::lock_guard<std::mutex> pk(g_pool_mu);
@@ -317,21 +330,30 @@ void geometry(int num_cus, uint32_t n_sets, uint32_t budget, uint32_t flags, uin
     if (*slices == 0) *slices = 1;
 }
 
-// Enqueue one search over batch B on stream st (B's device must be current).
+// Enqueue one search over batch B on stream st (B's device must be current).  With `link` it is
+// the linked search: the same phases, parts and geometry, the pf_check_linked_* kernels, the
+// link block reset in found[]'s place (d_found is then not touched).
 int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uint32_t timeout_ms,
-                  uint32_t* d_found, hipStream_t st) {
+                  uint32_t* d_found, hipStream_t st, const LinkArgs* link = nullptr, uint32_t n_link_groups = 0) {
     Dev* D = find_dev(B->device);
     unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
     uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
     // t0 and the profiling slots at the front, the work-queue heads of both launch parts from
     // PF_EARLY_QUEUE_OFF, the counter lines from PF_COUNTER_OFF: one fill for all
     {
-        const uint32_t nz = PF_SCRATCH_BYTES / 4, nf = (uint32_t)std::max<size_t>(B->n_sets, 1);
+        const uint32_t nz = PF_SCRATCH_BYTES / 4, nf = link ? 0u : (uint32_t)std::max<size_t>(B->n_sets, 1);
         const uint32_t blocks = std::min<uint32_t>((nz + nf + 255u) / 256u, 1024u);
         hipLaunchKernelGGL(pf_reset_kernel, dim3(blocks), dim3(256), 0, st, B->d_scratch, nz, d_found, nf);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(B->ev0, st));
+    if (link) {
+        const uint64_t n_rec = (uint64_t)n_link_groups * link->words;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_rec + n_link_groups + 255u) / 256u, 1024u);
+        hipLaunchKernelGGL(pf_link_init_kernel, dim3(blocks), dim3(256), 0, st, link->found, n_link_groups, link->mask,
+                           link->count, n_rec);
+        HIPCHK(hipGetLastError());
+    }
     const uint64_t deadline = timeout_ms ? (uint64_t)timeout_ms * 100000ull : 0ull;  // 100 MHz
     const bool early = flags & PF_FLAG_EARLY_EXIT;
     // phase 0: the probe (early exit, small batches: candidates 0..63 of every set, one wave
@@ -358,6 +380,14 @@ int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uin
         uint32_t* d_queue =
             B->d_scratch + PF_EARLY_QUEUE_OFF / 4 + (phase * 2 + part) * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;
         const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
+        if (link)
+            hipLaunchKernelGGL(part == 0 ? (early ? pf_check_linked_early_kernel : pf_check_linked_kernel)
+                                         : (early ? pf_check_linked_early_r16_kernel : pf_check_linked_r16_kernel),
+                               dim3(blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, B->d_order + first,
+                               (uint32_t)n, B->d_code, B->d_consts, B->d_schema, B->d_parents,
+                               gseed, pbudget, per_wave, slices, flags, deadline, d_t0, *link, d_counters,
+                               d_queue, cbegin);
+        else
         hipLaunchKernelGGL(part == 0 ? (early ? pf_check_early_kernel : pf_check_kernel)
                                      : (early ? pf_check_early_r16_kernel : pf_check_r16_kernel),
                            dim3(blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, B->d_order + first,
@@ -417,14 +447,18 @@ uint8_t* upload_staging(size_t bytes) {
 // Wait for B's last search on stream st and read its counters.
 // counters and kernel time of the last launch; with `found`, the verdicts too, copied before
 // the one stream synchronisation (a second round trip was ~4 % of a single query's search)
-int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_t>* found = nullptr) {
+// (d_from, n_from): the verdicts' device buffer and count when they are not the batch's found[]
+// (the linked search's group verdicts)
+int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_t>* found = nullptr,
+                  const uint32_t* d_from = nullptr, size_t n_from = 0) {
     constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
-    const size_t nf = std::max<size_t>(B->n_sets, 1);
+    const size_t nf = d_from ? n_from : std::max<size_t>(B->n_sets, 1);
+    if (!d_from) d_from = B->d_found;
     unsigned long long hs[PF_COUNTER_STRIPES * 16];
     uint8_t* pin = pinned_staging(cbytes + (found ? nf * 4 : 0));
     const uint32_t* d_counters = B->d_scratch + PF_COUNTER_OFF / 4;
     if (found) found->assign(nf, 0u);
-    if (found && pin && B->d_found == d_counters + cbytes / 4) {
+    if (found && pin && d_from == d_counters + cbytes / 4) {
         // the batch block keeps found[] right after the counter lines: one copy (each copy is
         // a blit dispatch serialised behind the search)
         HIPCHK(hipMemcpyAsync(pin, d_counters, cbytes + nf * 4, hipMemcpyDeviceToHost, st));
@@ -433,7 +467,7 @@ int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_
                               hipMemcpyDeviceToHost, st));
         if (found)
             HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin + cbytes) : static_cast<void*>(found->data()),
-                                  B->d_found, nf * 4, hipMemcpyDeviceToHost, st));
+                                  d_from, nf * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pin) {
@@ -749,6 +783,9 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         B->h_wide = std::move(pp.wide);
         B->h_sites = std::move(wo.sites);
         B->h_order = wo.order;
+        if (n_const && consts) B->h_link.consts.assign(consts, consts + 8 * n_const);
+        if (n_vars && schema) B->h_link.schema.assign(schema, schema + 4 * n_vars);
+        if (n_parents && parents) B->h_link.parents.assign(parents, parents + 8 * n_parents);
         B->d_mem = pool_acquire(Dv, total, &B->mem_cap);
         if (!B->d_mem) {
             delete B;
@@ -850,6 +887,81 @@ int pf_check_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint3
     std::vector<uint32_t> found;
     if (check_collect(B, D->stream, stats, &found)) return -1;
     return found_to_host(B, found, found_out, sat_bitmap_out, stats);
+}
+
+int pf_check_linked(uint64_t handle, uint64_t global_seed, uint32_t budget, uint32_t flags,
+                    uint32_t timeout_ms, const uint32_t* group_of, uint32_t n_groups,
+                    uint32_t* found_out, pf_stats* stats) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    Batch* B = as_batch(handle);
+    if (!B) return fail("pf_check_linked: null batch");
+    if (budget == 0) return fail("pf_check_linked: budget must be at least 1");
+    if (!found_out) return fail("pf_check_linked: null found_out");
+    if (B->n_sets == 0) return fail("pf_check_linked: the batch has no sets");
+    std::vector<uint32_t> parts;
+    {
+        const std::string e = link_validate(B->h_descs, B->h_link, group_of, n_groups, parts);
+        if (!e.empty()) return fail("%s", e.c_str());
+    }
+    const size_t ns = B->n_sets;
+    const uint32_t words = (uint32_t)(((uint64_t)budget + 63u) / 64u);
+    Dev* D = use_dev(B->device);
+    if (!D || switch_stream(D, D->stream)) return -1;
+    hipStream_t st = D->stream;
+    // the link block: [group_of: n_sets | parts: n_groups | found: n_groups | count: records | mask:
+    // records], records = n_groups x ceil(budget / 64); sized to the call, grown when one needs more
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t n_rec = (size_t)n_groups * words;
+    const size_t o_of = 0, o_parts = o_of + al(ns * 4), o_found = o_parts + al((size_t)n_groups * 4),
+                 o_count = o_found + al((size_t)n_groups * 4), o_mask = o_count + al(n_rec * 4),
+                 total = o_mask + al(n_rec * 8);
+    if (B->l_mem && B->l_cap < total) {
+        // nothing of this batch is in flight: every earlier call on it returned after its results
+        pool_release(D, B->l_mem, B->l_cap);
+        B->l_mem = nullptr;
+        B->l_req.clear();
+    }
+    if (!B->l_mem) {
+        B->l_mem = pool_acquire(D, total, &B->l_cap);
+        if (!B->l_mem) return fail("pf_check_linked: hipMalloc(%zu) failed", total);
+        B->l_req.clear();
+    }
+    uint8_t* lb = static_cast<uint8_t*>(B->l_mem);
+    LinkArgs L;
+    L.group_of = reinterpret_cast<uint32_t*>(lb + o_of);
+    L.parts = reinterpret_cast<uint32_t*>(lb + o_parts);
+    L.found = reinterpret_cast<uint32_t*>(lb + o_found);
+    L.count = reinterpret_cast<uint32_t*>(lb + o_count);
+    L.mask = reinterpret_cast<unsigned long long*>(lb + o_mask);
+    L.words = words;
+    // the tables move with the layout (n_groups), so a call uploads them unless it repeats the
+    // last call's grouping
+    std::vector<uint32_t> req(group_of, group_of + ns);
+    req.push_back(n_groups);
+    if (req != B->l_req) {
+        const size_t in_bytes = o_parts + (size_t)n_groups * 4;
+        // sized for the results too: check_collect must not replace the buffer under this copy
+        // (the stream orders its copies back after the upload has been consumed)
+        const size_t out_bytes = PF_COUNTER_STRIPES * 128 + (size_t)n_groups * 4;
+        uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
+        if (!pin) return fail("pf_check_linked: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
+        memcpy(pin + o_of, group_of, ns * 4);
+        memcpy(pin + o_parts, parts.data(), (size_t)n_groups * 4);
+        HIPCHK(hipMemcpyAsync(lb, pin, in_bytes, hipMemcpyHostToDevice, st));
+        B->l_req = std::move(req);
+    }
+    if (check_enqueue(B, global_seed, budget, flags, timeout_ms, nullptr, st, &L, n_groups)) return -1;
+    std::vector<uint32_t> found;
+    pf_stats local;
+    if (check_collect(B, st, &local, &found, L.found, n_groups)) return -1;
+    uint64_t n_sat = 0;
+    for (uint32_t g = 0; g < n_groups; g++) {
+        found_out[g] = found[g];
+        n_sat += found[g] != 0xffffffffu;
+    }
+    local.n_sat = n_sat;
+    if (stats) *stats = local;
+    return 0;
 }
 
 int pf_check_batches(const uint64_t* handles, size_t n, uint64_t global_seed, uint32_t budget,

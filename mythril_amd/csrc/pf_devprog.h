@@ -708,6 +708,58 @@ static inline WaveOrder wave_order(const uint32_t* code, const pf_set_desc* desc
     return R;
 }
 
+// ---- link groups (include/pf_bytecode.h, link contract) ---------------------------------
+// The host copies pf_batch_create keeps of what a link group's members must share: the device
+// descriptors (const_off into the device pool, whose ranges begin with the caller's n_const
+// constants), the device constant pool, the schema and the parent values.
+struct LinkTables {
+    std::vector<uint32_t> consts, schema, parents;
+};
+// What pf_check_linked checks before it launches anything: ids in range, no empty group, no
+// group above PF_LINK_MAX_PARTS, every member equal to its group's first in all the contract
+// names.  parts_out[g] = the members of group g.  Returns the error, empty when there is none.
+static inline std::string link_validate(const std::vector<pf_set_desc>& descs, const LinkTables& T,
+                                        const uint32_t* group_of, uint32_t n_groups,
+                                        std::vector<uint32_t>& parts_out) {
+    const size_t n_sets = descs.size();
+    if (n_groups == 0) return errorf("pf_check_linked: no groups");
+    if (!group_of) return errorf("pf_check_linked: null group_of");
+    std::vector<uint32_t> parts(n_groups, 0), first(n_groups, 0);
+    for (size_t s = 0; s < n_sets; s++) {
+        const uint32_t g = group_of[s];
+        if (g >= n_groups) return errorf("pf_check_linked: set %zu names group %u of %u", s, g, n_groups);
+        if (parts[g]++ == 0) first[g] = (uint32_t)s;
+    }
+    for (uint32_t g = 0; g < n_groups; g++) {
+        if (parts[g] == 0) return errorf("pf_check_linked: group %u is empty", g);
+        if (parts[g] > PF_LINK_MAX_PARTS)
+            return errorf("pf_check_linked: group %u has %u members (at most %u)", g, parts[g], PF_LINK_MAX_PARTS);
+    }
+    for (size_t s = 0; s < n_sets; s++) {
+        const pf_set_desc &a = descs[first[group_of[s]]], &b = descs[s];
+        if (&a == &b) continue;
+        const uint32_t g = group_of[s];
+        if (a.n_vars != b.n_vars) return errorf("pf_check_linked: group %u: set %zu has %u variables, not %u", g, s, b.n_vars, a.n_vars);
+        if (a.n_const != b.n_const) return errorf("pf_check_linked: group %u: set %zu has %u constants, not %u", g, s, b.n_const, a.n_const);
+        if (a.seed != b.seed) return errorf("pf_check_linked: group %u: set %zu has another seed", g, s);
+        if (a.n_const && memcmp(T.consts.data() + 8 * (size_t)a.const_off, T.consts.data() + 8 * (size_t)b.const_off,
+                                32 * (size_t)a.n_const))
+            return errorf("pf_check_linked: group %u: set %zu has other constants", g, s);
+        for (uint32_t v = 0; v < a.n_vars; v++) {
+            const uint32_t* sa = T.schema.data() + 4 * ((size_t)a.var_off + v);
+            const uint32_t* sb = T.schema.data() + 4 * ((size_t)b.var_off + v);
+            if (sa[0] != sb[0] || sa[1] != sb[1] || sa[2] != sb[2])
+                return errorf("pf_check_linked: group %u: set %zu variable %u has another schema entry", g, s, v);
+            if ((sa[3] == PF_NO_PARENT) != (sb[3] == PF_NO_PARENT) ||
+                (sa[3] != PF_NO_PARENT &&
+                 memcmp(T.parents.data() + 8 * (size_t)sa[3], T.parents.data() + 8 * (size_t)sb[3], 32)))
+                return errorf("pf_check_linked: group %u: set %zu variable %u has another parent value", g, s, v);
+        }
+    }
+    parts_out = std::move(parts);
+    return std::string();
+}
+
 }  // namespace pf_devprog
 
 #endif /* PF_DEVPROG_H */

@@ -1121,13 +1121,104 @@ PF_INL void search_item(const SetCtx& S, uint32_t set, uint32_t begin, uint32_t 
     }
 }
 
+// ---- linked search (include/pf_bytecode.h, link contract) -------------------------------
+// The batch's link block (pathfeas.hip): per link group its verdict, and per group and 64
+// candidates one record — the AND of the members' ballots (all ones before a call) and the
+// members that have arrived.
+struct LinkArgs {
+    const uint32_t* group_of;  // set -> link group
+    const uint32_t* parts;     // link group -> members
+    unsigned long long* mask;  // [group][words]
+    uint32_t* count;           // [group][words]
+    uint32_t* found;           // [group]
+    uint32_t words;            // records per group: ceil(budget / 64)
+};
+
+// search_item for a member of a link group: the wave ANDs its ballot into the record of (group,
+// 64 candidates) and counts itself; the member that arrives last reads the mask and posts the
+// group's smallest witness there.  Release before the count, acquire after it, at device scope;
+// every shared word is written by an atomic and read by an atomic load, one lane issues them and
+// no wave waits for another.  A record whose mask an earlier member already cleared is not
+// evaluated (one load), but still counted: the arrival count is what says a record is final, so
+// a later reader of count == parts may rely on the mask.  The wave leaves the item only on the
+// group's verdict (a member's own hit says nothing about the others) or at the deadline — a cut
+// item's records stay short of `parts` arrivals and are never posted.  A group of one posts its
+// ballot directly, as search_item does, and touches no record.
+template <bool EARLY, int NREG>
+PF_INL void linked_item(const SetCtx& S, const LinkArgs& L, uint32_t set, uint32_t begin, uint32_t end,
+                        uint32_t flags, uint64_t deadline_ticks, uint64_t t0, uint2* exp_tbl,
+                        uint64_t& evals_full, uint64_t& decided, uint64_t& ops, uint32_t& cut, UnitProf& prof) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t g = __builtin_amdgcn_readfirstlane(L.group_of[set]);
+    const uint32_t parts = __builtin_amdgcn_readfirstlane(L.parts[g]);
+    uint32_t* gfound = L.found + g;
+    bool posted = false;
+    for (uint32_t base = begin; base < end; base += 64u) {
+        if (EARLY) {
+            uint32_t f = __hip_atomic_load(gfound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__builtin_amdgcn_readfirstlane(f) <= base) break;
+        }
+        if (deadline_ticks) {
+            uint64_t now = __builtin_amdgcn_s_memrealtime();
+            if (now - t0 > deadline_ticks) {
+                cut = 1u;
+                break;
+            }
+        }
+        const size_t rec = (size_t)g * L.words + (base >> 6);
+        uint32_t live = 1u;
+        if (parts > 1u && lane == 0u)
+            live = __hip_atomic_load(L.mask + rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull;
+        live = __builtin_amdgcn_readfirstlane(live);
+        uint64_t m_sat = 0ull;
+        if (live) {
+            const uint32_t cand = base + lane;
+            const bool active = cand < end;
+            uint32_t complete = 0;
+            uint64_t lane_ops = 0;
+            uint32_t sat = run_program<MODE_GEN, NREG>(S, cand, active, flags, nullptr, 0u, exp_tbl, &complete,
+                                                       &lane_ops, &prof);
+            const uint64_t m_act = pf::wave_mask(active);
+            m_sat = m_act & pf::wave_mask(sat != 0u);
+            const uint64_t m_full = m_act & pf::wave_mask(complete != 0u);
+            decided += __popcll(m_act);
+            evals_full += __popcll(m_full);
+            ops += lane_ops * (uint64_t)__popcll(m_act);
+        }
+        if (parts == 1u) {
+            if (m_sat && !posted) {
+                if (lane == 0) atomicMin(gfound, base + (uint32_t)__builtin_ctzll(m_sat));
+                posted = true;
+                if (EARLY) break;
+            }
+            continue;
+        }
+        if (lane == 0) {
+            if (live && m_sat != ~0ull)
+                (void)__hip_atomic_fetch_and(L.mask + rec, m_sat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            const uint32_t before = __hip_atomic_fetch_add(L.count + rec, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (before + 1u == parts) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                const uint64_t m = __hip_atomic_load(L.mask + rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (m) {
+                    const uint32_t first = base + (uint32_t)__builtin_ctzll(m);
+                    if (__hip_atomic_load(gfound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > first)
+                        atomicMin(gfound, first);
+                }
+            }
+        }
+    }
+}
+
 // ---- search kernel: generate + evaluate + ballot early exit ---------------------------
 // grid: a chip-filling set of persistent waves that take (set, slice) items from a work
 // queue; a slice is `per_wave` consecutive candidates.
 // Two entry points over one body: the full sweep (pf_check_kernel) and the production
 // early-exit search (pf_check_early_kernel).  EARLY is a template constant so the full sweep
 // carries no found[] polling, and the two launches are separate rows in a rocprof trace.
-template <bool EARLY, int NREG>
+// LINK (the pf_check_linked_* entry points) swaps the item for linked_item; nothing else differs.
+template <bool EARLY, int NREG, bool LINK = false>
 PF_INL void check_body(const pf_set_desc* __restrict__ descs, const uint32_t* __restrict__ order,
                        uint32_t n_sets,
                        const uint4* __restrict__ code, const uint32_t* __restrict__ consts,
@@ -1135,7 +1226,7 @@ PF_INL void check_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
                        uint64_t gseed, uint32_t budget, uint32_t per_wave, uint32_t slices,
                        uint32_t flags, uint64_t deadline_ticks, uint64_t* __restrict__ t0_slot,
                        uint32_t* __restrict__ found, unsigned long long* __restrict__ counters,
-                       uint32_t* __restrict__ queue, uint32_t cand_begin) {
+                       uint32_t* __restrict__ queue, uint32_t cand_begin, const LinkArgs link = LinkArgs()) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const uint32_t n_items = n_sets * slices;
@@ -1197,6 +1288,11 @@ PF_INL void check_body(const pf_set_desc* __restrict__ descs, const uint32_t* __
             // early exit: chunk-major; full sweep: set-major, sets longest first
             const uint32_t set = __builtin_amdgcn_readfirstlane(order[EARLY ? item % n_sets : item / slices]);
             const uint32_t slice = EARLY ? item / n_sets : item % slices;
+            if constexpr (LINK)
+                linked_item<EARLY, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), link, set,
+                                         cand_begin + slice * per_wave, min(budget, cand_begin + slice * per_wave + per_wave),
+                                         flags, deadline_ticks, t0, exp_tbl, evals_full, decided, ops, cut, prof);
+            else
             search_item<EARLY, NREG>(make_ctx(descs, set, code, consts, schema, parents, gseed), set,
                                      cand_begin + slice * per_wave, min(budget, cand_begin + slice * per_wave + per_wave), flags,
                                      deadline_ticks, t0, found, exp_tbl, evals_full, decided, ops, cut, prof);
@@ -1260,6 +1356,47 @@ extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_
 }
 extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_check_early_r16_kernel(PF_CHECK_PARAMS) {
     check_body<true, 16>(PF_CHECK_ARGS);
+}
+
+// The linked search's entry points: the four above with the link block's tables in place of
+// found[].  Either register file's launch may hold a record's last arrival.
+#define PF_LINKED_PARAMS                                                                      \
+    const pf_set_desc *__restrict__ descs, const uint32_t *__restrict__ order, uint32_t n_sets, \
+        const uint4 *__restrict__ code, const uint32_t *__restrict__ consts,                   \
+        const uint4 *__restrict__ schema, const uint32_t *__restrict__ parents, uint64_t gseed, \
+        uint32_t budget, uint32_t per_wave, uint32_t slices, uint32_t flags,                   \
+        uint64_t deadline_ticks, uint64_t *__restrict__ t0_slot, LinkArgs link,                \
+        unsigned long long *__restrict__ counters, uint32_t *__restrict__ queue, uint32_t cand_begin
+#define PF_LINKED_ARGS                                                                        \
+    descs, order, n_sets, code, consts, schema, parents, gseed, budget, per_wave, slices, flags, \
+        deadline_ticks, t0_slot, nullptr, counters, queue, cand_begin, link
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_check_linked_kernel(PF_LINKED_PARAMS) {
+    check_body<false, PF_NW_NARROW + 1, true>(PF_LINKED_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU_NARROW) pf_check_linked_early_kernel(PF_LINKED_PARAMS) {
+    check_body<true, PF_NW_NARROW + 1, true>(PF_LINKED_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_check_linked_r16_kernel(PF_LINKED_PARAMS) {
+    check_body<false, 16, true>(PF_LINKED_ARGS);
+}
+extern "C" __global__ void __launch_bounds__(64 * PF_SEARCH_WG_WAVES, PF_WG_PER_CU) pf_check_linked_early_r16_kernel(PF_LINKED_PARAMS) {
+    check_body<true, 16, true>(PF_LINKED_ARGS);
+}
+
+// Per-call reset of a batch's link block: every group's verdict to "none", every record's mask
+// to all ones and its arrival count to 0.
+extern "C" __global__ void __launch_bounds__(256) pf_link_init_kernel(uint32_t* __restrict__ found, uint32_t n_groups,
+                                                                      unsigned long long* __restrict__ mask,
+                                                                      uint32_t* __restrict__ count, uint64_t n_rec) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rec + n_groups; i += stride) {
+        if (i < n_rec) {
+            mask[i] = ~0ull;
+            count[i] = 0u;
+        } else {
+            found[i - n_rec] = 0xFFFFFFFFu;
+        }
+    }
 }
 
 // ---- climb: scored rounds over near misses (include/pf_bytecode.h, climb contract) ------

@@ -174,20 +174,65 @@ class Engine:
         return CheckResult(found[:n], st.evals_full, st.cands_decided, st.ops, st.kernel_ms,
                            bool(st.timed_out))
 
-    def upload_sharded(self, programs: Sequence[Program]) -> List[DeviceBatch]:
+    def check_linked(self, db: DeviceBatch, group_of: Sequence[int], budget: int = 65536, seed: int = 0,
+                     flags: int = 2, timeout_ms: int = 0) -> CheckResult:
+        """Linked search (pf_check_linked; include/pf_bytecode.h, link contract): ``group_of[s]``
+        is set s's link group, ``found[g]`` of the result the smallest candidate at which every
+        member of group g holds.  The members of a group share schema, constants, parents and
+        seed (lower_parts makes them so), hence ``materialize`` of any member at the verdict is
+        the group's assignment."""
+        ids = np.ascontiguousarray([int(g) & 0xFFFFFFFF for g in group_of], dtype=np.uint32)
+        if len(ids) != len(db):
+            raise _lib.PathFeasError(f"check_linked: {len(ids)} group ids for {len(db)} sets")
+        n_groups = int(ids.max()) + 1 if len(ids) else 0
+        found = np.full(max(n_groups, 1), NOT_FOUND, dtype=np.uint32)
+        st = _lib.pf_stats()
+        _lib.check(_lib.lib().pf_check_linked(db.handle, seed, budget, flags, timeout_ms,
+                                             _lib.ptr_u32(ids) if len(ids) else None, n_groups,
+                                             _lib.ptr_u32(found), ctypes.byref(st)), "pf_check_linked")
+        return CheckResult(found[:n_groups], st.evals_full, st.cands_decided, st.ops, st.kernel_ms,
+                           bool(st.timed_out))
+
+    def upload_sharded(self, programs: Sequence[Program], group_of: Optional[Sequence[int]] = None):
         """Size-balanced contiguous shards, one per device (mythril_amd.dist.shard_bounds
-        over the bytecode cost model), each uploaded to its device."""
+        over the bytecode cost model), each uploaded to its device.  With ``group_of`` — the
+        programs' link groups, each group's members adjacent — the cuts fall between groups, so a
+        group's members stay on one device, and the result is (batches, per batch its members'
+        groups renumbered from 0) for check_linked."""
         from .dist import shard_bounds
 
         progs = list(programs)
         nd = len(self.devices)
-        if nd == 1 or len(progs) < 2:
-            return [self.upload(progs)]
-        out = []
-        for (lo, hi), d in zip(shard_bounds([p.sched_cost() for p in progs], nd), self.devices):
-            if hi > lo:
-                out.append(self.upload(progs[lo:hi], device=d))
-        return out
+        if group_of is None:
+            if nd == 1 or len(progs) < 2:
+                return [self.upload(progs)]
+            out = []
+            for (lo, hi), d in zip(shard_bounds([p.sched_cost() for p in progs], nd), self.devices):
+                if hi > lo:
+                    out.append(self.upload(progs[lo:hi], device=d))
+            return out
+        gids = [int(g) for g in group_of]
+        if len(gids) != len(progs):
+            raise _lib.PathFeasError(f"upload_sharded: {len(gids)} group ids for {len(progs)} programs")
+        runs = []      # [first program, end) of every group, in order
+        for i, g in enumerate(gids):
+            if runs and gids[runs[-1][0]] == g:
+                runs[-1][1] = i + 1
+            else:
+                runs.append([i, i + 1])
+        if len({gids[lo] for lo, _ in runs}) != len(runs):
+            raise _lib.PathFeasError("upload_sharded: a link group's members must be adjacent")
+        costs = [sum(p.sched_cost() for p in progs[lo:hi]) for lo, hi in runs]
+        bounds = [(0, len(runs))] if nd == 1 or len(runs) < 2 else shard_bounds(costs, nd)
+        dbs, local = [], []
+        for (lo, hi), d in zip(bounds, self.devices):
+            if hi <= lo:
+                continue
+            p0, p1 = runs[lo][0], runs[hi - 1][1]
+            dbs.append(self.upload(progs[p0:p1], device=d))
+            renum = {gids[runs[r][0]]: r - lo for r in range(lo, hi)}
+            local.append([renum[g] for g in gids[p0:p1]])
+        return dbs, local
 
     def check_many(self, dbs: Sequence[DeviceBatch], budget: int = 65536, seed: int = 0,
                    flags: int = 2, timeout_ms: int = 0) -> CheckResult:

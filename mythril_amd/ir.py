@@ -169,6 +169,15 @@ CENSUS_CUT = 1
 CENSUS_MAX_SITES = 0xFFFF
 CENSUS_UNKNOWN = 0xFFFFFFFF
 
+# ---- link contract (include/pf_bytecode.h) ------------------------------------------
+# A link group is a non-empty list of at most LINK_MAX_PARTS sets of one batch that agree in
+# n_vars and every variable's kind, width and hints, in n_const and their first n_const constants
+# (the caller's pool), in seed, and in parents (per variable none, or the same value): they see
+# one candidate stream.  Candidate c is the group's witness iff every member's root holds under
+# it; the group's verdict is the smallest such c in [0, budget) or 0xFFFFFFFF, and a group of one
+# has that set's plain verdict.  lower_parts (mythril_amd/lower.py) makes such groups.
+LINK_MAX_PARTS = 64
+
 # ---- algorithmic int32-op cost table -----------------------------
 # Ops not in the table (moves, constant loads, candidate generation) cost 0: they are
 # bookkeeping, not constraint arithmetic.  Width-generic ops scale by ceil(w/32)/8.

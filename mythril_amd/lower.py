@@ -481,6 +481,72 @@ def lower(dag: Dag, seed: int = 0, name: str = "", nw: Optional[int] = None) -> 
     return ir.PackedProgram(code[:ni.value].copy(), cvals, list(dag.vars), seed, name)
 
 
+def _root_costs(prog) -> List[int]:
+    """Instructions the program spends per root: the stretch up to and including each ASSERT
+    (the lowering emits one per root, in root order)."""
+    if isinstance(prog, ir.PackedProgram):
+        ops = (prog.words[:, 0] & 0xFF).tolist()
+    else:
+        ops = [ins.op for ins in prog.code]
+    out, last = [], -1
+    for i, op in enumerate(ops):
+        if op == ir.ASSERT:
+            out.append(i - last)
+            last = i
+    return out
+
+
+def part_bounds(costs: Sequence[int], n_parts: int) -> List[Tuple[int, int]]:
+    """At most ``n_parts`` contiguous, non-empty [lo, hi) ranges over the roots, balanced by
+    cost: a part ends at the first root at which the running cost reaches the next multiple of
+    total / n_parts."""
+    n = len(costs)
+    n_parts = max(1, min(int(n_parts), n))
+    total = max(1, sum(costs))
+    out, lo, acc, k = [], 0, 0, 1
+    for i, c in enumerate(costs[:-1]):
+        acc += c
+        if acc * n_parts >= total * k:
+            out.append((lo, i + 1))
+            lo = i + 1
+            k = acc * n_parts // total + 1   # a root that crosses several marks makes one cut
+    out.append((lo, n))
+    return out
+
+
+def lower_parts(dag: Dag, n_parts: int, seed: int = 0, name: str = "", whole: Optional[Program] = None) -> List[Program]:
+    """The DAG's conjunction as at most ``n_parts`` programs for a linked search
+    (include/pf_bytecode.h, link contract): the roots, in order, in contiguous groups balanced by
+    the instructions ``lower(dag)`` spends on each (side constraints are roots like any other),
+    every root in exactly one part.  Each part carries the variables, the constant pool (same
+    order, same length), the parents and the seed of the program ``lower(dag)`` returns
+    (``whole``, when the caller has it), so the parts draw that program's candidates; each picks
+    its register file as ``lower`` does; a subterm two parts need is emitted in both.  Hints are
+    the caller's business, once, on the whole DAG before the split (seed.apply_hints): the hint
+    model is then every part's candidate 0."""
+    if n_parts < 1 or n_parts > ir.LINK_MAX_PARTS:
+        raise ValueError(f"lower_parts: {n_parts} parts (1 .. {ir.LINK_MAX_PARTS})")
+    if whole is None:
+        whole = lower(dag, seed, name)
+    costs = _root_costs(whole)
+    if len(costs) != len(dag.roots):
+        raise LoweringError(f"lower_parts: {len(costs)} asserts for {len(dag.roots)} roots")
+    if not dag.roots:
+        return [whole]
+    parts = []
+    bounds = part_bounds(costs, n_parts)
+    for k, (lo, hi) in enumerate(bounds):
+        # the same nodes and variables; the whole program's pool pinned, so no part adds to it
+        sub = Dag(nodes=dag.nodes, roots=list(dag.roots[lo:hi]), vars=dag.vars, forced=list(whole.consts))
+        sub._words_done = True
+        part = lower(sub, seed, f"{name}#{k}of{len(bounds)}" if name else f"#{k}of{len(bounds)}")
+        if len(part.consts) != len(whole.consts):
+            raise LoweringError("lower_parts: a part added to the constant pool")
+        part.link_roots = (lo, hi)
+        parts.append(part)
+    return parts
+
+
 def lower_py(dag: Dag, seed: int = 0, name: str = "", nw: int = ir.NW) -> Program:
     """Python reference of the lowering (the native library reproduces it exactly)."""
     prog = Program(vars=list(dag.vars), seed=seed, name=name)

@@ -28,7 +28,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .. import ir, seed
-from ..lower import LoweringError, lower
+from ..lower import LoweringError, _spill_code, lower, lower_parts
 from .independence import buckets
 from .interp import Witness
 from .model import WitnessModel
@@ -88,6 +88,15 @@ class GpuConfig:
     # how the climb scores a candidate (ir.CLIMB_SCORES): "sites", distances at fused compares
     # only, or "tree", distances carried through NOT / AND / OR / XOR / ITE above the compares
     climb_score: str = os.environ.get("PF_CLIMB_SCORE", "sites")
+    # linked search (include/pf_bytecode.h, link contract): a bucket whose unsplit program has at
+    # least `link_min_ins` instructions is lowered as up to `link_parts` programs over disjoint
+    # groups of its roots (lower.lower_parts) and searched by Engine.check_linked, one wave per
+    # part and 64 candidates instead of one walking the whole program; every other bucket of the
+    # call is a group of one in the same call.  The verdict, and so every answer, is the unsplit
+    # search's by contract.  0 = off, the default: check_sets then makes the calls it always made.
+    # A linked bucket that misses is not climbed (the climb is defined on unsplit programs).
+    link_min_ins: int = int(os.environ.get("PF_LINK_MIN_INS", "0"))
+    link_parts: int = int(os.environ.get("PF_LINK_PARTS", "8"))
 
 
 CONFIG = GpuConfig()
@@ -155,6 +164,8 @@ def _neg_key(key: tuple, cfg: GpuConfig) -> tuple:
     # ... under this configuration: a bucket the climb also left unanswered is negative only
     # for searches that climb the same way
     # (and scores them the same way: what one score left is not negative for the other)
+    # (the link knobs are not part of the key: a group's verdict is its unsplit program's by
+    # contract, so no answer depends on them)
     climb = (cfg.climb_rounds, cfg.climb_candidates) if cfg.climb_rounds > 0 else (0, 0)
     if cfg.climb_rounds > 0 and cfg.climb_score != "sites":
         climb += (cfg.climb_score,)
@@ -266,7 +277,7 @@ def _set_seed(constraints: Sequence[T.Term]) -> int:
 _NATIVE_TERMS = os.environ.get("PF_NATIVE_TERMS", "1") != "0"
 
 
-def _witness_limbs(eng, db, mine: List[int], base: int, progs, found, seed_: int) -> np.ndarray:
+def _witness_limbs(eng, db, mine: List[int], base: int, progs, found, seed_: int, set_of=None) -> np.ndarray:
     """The witnesses' variables as limb rows, in ``mine`` order.  When every witness of the
     batch is candidate 0 of a program whose variables all carry parent values (a single
     query whose hint model holds), those values are the rows (the generator keeps them at
@@ -283,7 +294,9 @@ def _witness_limbs(eng, db, mine: List[int], base: int, progs, found, seed_: int
             parts.append(rows)
         else:
             return np.concatenate(parts) if parts else np.zeros((0, 8), dtype=np.uint32)
-    return eng.materialize_limbs(db, [k - base for k in mine], [int(found[k]) for k in mine], seed=seed_)
+    # set_of: the batch set that stands for search entry k (a linked bucket's first part)
+    return eng.materialize_limbs(db, [(set_of[k] if set_of else k) - base for k in mine],
+                                 [int(found[k]) for k in mine], seed=seed_)
 
 
 def _probe_candidate0(eng, progs, lows, keys, reg, cfg) -> Dict[int, np.ndarray]:
@@ -361,20 +374,45 @@ def _native_batch() -> bool:
     return native_terms.batch_api() is not None
 
 
-def _lower_bucket(bucket: List[T.Term], reg: UFRegistry, parent: Optional[dict], hints: bool):
+def _attach_parts(prog, dag, link) -> None:
+    """prog.link_parts = the program's parts for a linked search, when the link knob is on, the
+    program is long enough and it splits; a split that fails to lower leaves the bucket unsplit."""
+    min_ins, n_parts = link
+    if min_ins <= 0 or _spill_code(prog)[0] < min_ins:
+        return
+    try:
+        parts = lower_parts(dag() if callable(dag) else dag, max(1, min(n_parts, ir.LINK_MAX_PARTS)),
+                            prog.seed, prog.name, prog)
+    except (LoweringError, ValueError, OverflowError):
+        return
+    if len(parts) > 1:
+        prog.link_parts = parts
+
+
+def _lower_bucket(bucket: List[T.Term], reg: UFRegistry, parent: Optional[dict], hints: bool, link=(0, 0)):
     """Terms -> (witness metadata, program): natively in libpflower.so when it is built
     (smt/native_terms.py, the same program node for node), else the Python reference
-    (to_dag.TermLowering -> seed.apply_hints -> lower.lower)."""
+    (to_dag.TermLowering -> seed.apply_hints -> lower.lower).  ``link`` = (link_min_ins,
+    link_parts): a long program also carries its parts (``link_parts``), lowered from the same
+    DAG after the hints."""
     if _NATIVE_TERMS:
         from . import native_terms
 
         if native_terms.store() is not None:
-            return native_terms.lower_bucket(bucket, reg, parent, hints, _set_seed(bucket))
+            if link[0] <= 0:
+                return native_terms.lower_bucket(bucket, reg, parent, hints, _set_seed(bucket))
+            r = native_terms.lower_native(bucket, reg, parent, native_terms.PROGRAM | (native_terms.HINTS if hints else 0),
+                                          _set_seed(bucket))
+            prog = r.program(_set_seed(bucket))
+            _attach_parts(prog, lambda: native_terms.dag_of(r), link)
+            return r.lowered(), prog
     tl = TermLowering(reg, parent)
     lo = tl.lower(bucket)
     if hints:
         seed.apply_hints(lo.dag)
-    return lo, lower(lo.dag, seed=_set_seed(bucket))
+    prog = lower(lo.dag, seed=_set_seed(bucket))
+    _attach_parts(prog, lo.dag, link)
+    return lo, prog
 
 
 _CLIMB_IDX = 0xFFFFFFFE   # found_all[] of a bucket whose witness is a climb's assignment
@@ -396,11 +434,12 @@ def _origin(idx: int, prog, hinted: bool, parented: bool) -> str:
 def _lower_chunk(job):
     """Worker: lower a chunk of buckets; the DAG stays behind (witnesses need only the
     variable / UF / array-read terms)."""
-    items, reg, hints = job
+    items, reg, hints = job[:3]
+    link = job[3] if len(job) > 3 else (0, 0)
     out = []
     for bucket, parent in items:
         try:
-            lo, prog = _lower_bucket(bucket, reg, parent, hints)
+            lo, prog = _lower_bucket(bucket, reg, parent, hints, link)
             out.append((Lowered(None, lo.var_terms, lo.uf_apps, lo.array_reads), prog, None))
             lo = None
         except (LoweringError, ValueError, OverflowError, RecursionError) as e:
@@ -459,9 +498,9 @@ def _lower_all(jobs, reg: UFRegistry, cfg: GpuConfig):
     """[(bucket, parent)] -> [(Lowered | None, Program | None, error | None)], in order."""
     n = min(cfg.workers, len(jobs))
     if n <= 1 or len(jobs) < cfg.parallel_min:
-        return _lower_chunk((jobs, reg, cfg.hints))
+        return _lower_chunk((jobs, reg, cfg.hints, (cfg.link_min_ins, cfg.link_parts)))
     per = max(1, (len(jobs) + 4 * n - 1) // (4 * n))
-    chunks = [(jobs[i:i + per], reg, cfg.hints) for i in range(0, len(jobs), per)]
+    chunks = [(jobs[i:i + per], reg, cfg.hints, (cfg.link_min_ins, cfg.link_parts)) for i in range(0, len(jobs), per)]
     out = []
     for part in _pool(n).map(_lower_chunk, chunks):
         out.extend(part)
@@ -473,7 +512,7 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                config: Optional[GpuConfig] = None) -> List[Optional[WitnessModel]]:
     import time
 
-    from ..engine import get_engine  # the GPU is required from here on: no host fallback
+    from ..engine import CheckResult, get_engine  # the GPU is required from here on: no host fallback
 
     cfg = config or CONFIG
     reg = registry or DEFAULT_REGISTRY
@@ -590,6 +629,9 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
             found[key] = None
             failed.add(key)
             continue
+        if nat and cfg.link_min_ins > 0 and getattr(prog, "native_result", None) is not None:
+            _attach_parts(prog, lambda r=prog.native_result: native_terms.dag_of(r),
+                          (cfg.link_min_ins, cfg.link_parts))
         todo[key] = len(progs)
         progs.append(prog)
         lows.append(lo)
@@ -619,8 +661,27 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
         limb_rows = []   # native: the witnesses' variables as limbs, in `sat` order
         if search:
             sprogs = [progs[k] for k in search]
-            # one batch per device of the engine (cost-balanced shards), searched concurrently
-            dbs = eng.upload_sharded(sprogs) if hasattr(eng, "upload_sharded") else [eng.upload(sprogs)]
+            # linked search: the long buckets as their parts, every other bucket a group of one;
+            # set_of[i] = the uploaded set that stands for search entry i (a group's first member:
+            # the members share their variables, so its assignment is the group's)
+            linked = cfg.link_min_ins > 0 and hasattr(eng, "check_linked") and any(
+                getattr(p, "link_parts", None) for p in sprogs)
+            set_of = list(range(len(sprogs)))
+            is_split = [False] * len(sprogs)
+            if linked:
+                uprogs, group_of = [], []
+                for g, p in enumerate(sprogs):
+                    members = getattr(p, "link_parts", None) or [p]
+                    set_of[g], is_split[g] = len(uprogs), len(members) > 1
+                    uprogs += members
+                    group_of += [g] * len(members)
+                if hasattr(eng, "upload_sharded"):
+                    dbs, groups_of = eng.upload_sharded(uprogs, group_of)   # a group stays on one device
+                else:
+                    dbs, groups_of = [eng.upload(uprogs)], [group_of]
+            else:
+                # one batch per device of the engine (cost-balanced shards), searched concurrently
+                dbs = eng.upload_sharded(sprogs) if hasattr(eng, "upload_sharded") else [eng.upload(sprogs)]
             lap("upload")
             flags = cfg.flags
             if nat and cfg.hints and any(_long_hint_miss(p, cfg.probe_min_ins) for p in sprogs):
@@ -628,7 +689,16 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                 # vain before the search walks it again
                 flags |= ir.FLAG_NO_PROBE
             t_dev = time.perf_counter()
-            if len(dbs) == 1:
+            if linked:
+                # the devices' groups are consecutive runs of the call's, so the verdicts
+                # concatenate; the batches are searched one after the other
+                rs = [eng.check_linked(db, g, budget=cfg.budget, seed=cfg.seed, flags=flags,
+                                       timeout_ms=cfg.timeout_ms) for db, g in zip(dbs, groups_of)]
+                res = rs[0] if len(rs) == 1 else CheckResult(
+                    np.concatenate([r.found for r in rs]), sum(r.evals_full for r in rs),
+                    sum(r.cands_decided for r in rs), sum(r.ops for r in rs), sum(r.kernel_ms for r in rs),
+                    any(r.timed_out for r in rs))
+            elif len(dbs) == 1:
                 res = eng.check(dbs[0], budget=cfg.budget, seed=cfg.seed, flags=flags,
                                 timeout_ms=cfg.timeout_ms)
             else:
@@ -639,7 +709,8 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
             for i, k in enumerate(search):
                 found_all[k] = res.found[i]
             ssat = [i for i in range(len(search)) if res.found[i] != 0xFFFFFFFF]
-            missed = [i for i in range(len(search)) if res.found[i] == 0xFFFFFFFF]
+            # (a linked bucket that misses is not climbed: the climb is defined on unsplit programs)
+            missed = [i for i in range(len(search)) if res.found[i] == 0xFFFFFFFF and not is_split[i]]
             climb_on = cfg.climb_rounds > 0 and cfg.climb_candidates > 0 and missed and not timed_out \
                 and hasattr(eng, "climb")
             # one deadline for the call's device work: the climb gets what the search left of
@@ -655,7 +726,7 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                 # assignment (no candidate index of the search), taken from here on like any
                 # other witness — re-checked on the host, cached, noted
                 how = {} if cfg.climb_score == "sites" else {"score": cfg.climb_score}
-                cl = eng.climb(dbs if len(dbs) > 1 else dbs[0], missed, cfg.climb_rounds,
+                cl = eng.climb(dbs if len(dbs) > 1 else dbs[0], [set_of[i] for i in missed], cfg.climb_rounds,
                                cfg.climb_candidates, seed=cfg.seed, timeout_ms=climb_ms_left, **how)
                 timed_out = timed_out or bool(cl.timed_out)
                 n_climb_sat = 0
@@ -673,18 +744,19 @@ def check_sets(sets: Sequence[Sequence[T.Term]], registry: Optional[UFRegistry] 
                 lap("climb")
             base = 0
             for db in dbs:
-                mine = [i for i in ssat if base <= i < base + len(db)]
+                mine = [i for i in ssat if base <= set_of[i] < base + len(db)]
                 if mine:
-                    sids, cids = [i - base for i in mine], [int(res.found[i]) for i in mine]
+                    sids, cids = [set_of[i] - base for i in mine], [int(res.found[i]) for i in mine]
                     if nat:
                         if hasattr(eng, "materialize_limbs"):
-                            rows = _witness_limbs(eng, db, mine, base, sprogs, res.found, cfg.seed)
+                            rows = _witness_limbs(eng, db, mine, base, sprogs, res.found, cfg.seed,
+                                                  set_of if linked else None)
                         else:
                             rows = ir.limbs_array([x for vs in eng.materialize(db, sids, cids, seed=cfg.seed)
                                                    for x in vs])
                         o = 0
                         for i in mine:
-                            nv = int(db.batch.descs[i - base][5])
+                            nv = int(db.batch.descs[set_of[i] - base][5])
                             vals_of[search[i]] = rows[o:o + nv]
                             o += nv
                     else:

@@ -497,6 +497,36 @@ def lower_bucket(bucket: List[T.Term], reg: UFRegistry, parent: Optional[dict], 
     return r.lowered(), r.program(seed)
 
 
+def dag_of(r: "_Result"):
+    """The native DAG of a result — nodes, roots, variables (hints applied when the result was
+    lowered with HINTS), pinned constants — as a mythril_amd.lower.Dag."""
+    from .. import lower as LW
+
+    kinds = {v: k for k, v in LW._KIND_CODE.items()}
+    nn = r.info[8]
+    pool = [_int_of(x) for x in r.get(GET_POOL, r.info[9], 8).tolist()]
+    dag = LW.Dag(vars=r.variables())
+    for kind, width, la, a0, a1, a2, aux, is_bool in r.get(GET_NODES, nn, 8).tolist():
+        k = kinds.get(kind, kind)
+        dag.nodes.append(LW.Node(k, width, (a0, a1, a2)[:la], pool[aux] if k == LW.K_CONST else aux, bool(is_bool)))
+    dag.roots = [int(x) for x in r.get(GET_ROOTS, r.info[10], 1)]
+    dag.forced = [_int_of(x) for x in r.get(GET_FORCED, r.info[11], 8).tolist()]
+    dag._words_done = True
+    return dag
+
+
+def lower_parts(bucket: List[T.Term], reg: UFRegistry, parent: Optional[dict], hints: bool, seed: int,
+                n_parts: int) -> Tuple[Lowered, ir.PackedProgram, List[ir.Program]]:
+    """lower_bucket plus the bucket's parts for a linked search (mythril_amd.lower.lower_parts):
+    terms, DAG, hints and the unsplit program natively; the parts are lowered by pfl_lower from
+    that DAG's own node table, so they are the Python pipeline's parts node for node."""
+    from .. import lower as LW
+
+    r = lower_native(bucket, reg, parent, PROGRAM | (HINTS if hints else 0), seed)
+    whole = r.program(seed)
+    return r.lowered(), whole, LW.lower_parts(dag_of(r), n_parts, seed, "", whole)
+
+
 def recheck(bucket: List[T.Term], lo: Lowered, values: List[int], reg: UFRegistry) -> Optional[bool]:
     """The host re-check of a bucket witness natively (pflt_recheck, csrc/pf_recheck.cpp):
     every conjunct true under the witness (interp.Witness's interpretation).  None when the

@@ -7,7 +7,9 @@ built with the address and undefined-behaviour sanitizers and run as a child pro
   - the multi-digit division against the oracle's: twelve pairs that take algorithm D's add-back
     step (widths 256, 160, 255, all five division ops) and 2,000 pairs of extreme digits,
   - EXP at every width over the edges of powmod's shortcuts, MUL at 256 bits,
-  - PF_W_HASH against the oracle's, CRC-32 against zlib's.
+  - PF_W_HASH against the oracle's, CRC-32 against zlib's,
+  - the op-by-op section again at each of the other 251 widths of 1..256, and every arithmetic op
+    and compare on the 8-row lists of tests/width_cases.py at every width.
 CPU only."""
 
 import os
@@ -18,6 +20,7 @@ import zlib
 
 import pyoracle as O
 import pytest
+import width_cases as WC
 from conftest import ROOT, load_golden
 from test_gpu_parity import _CMPS, _OPS
 
@@ -90,8 +93,7 @@ def _cases():
         case(op, v["w"], 0, int(v["a"], 16), int(v["b"], 16), r)
     n_golden = len(out)
 
-    rng = random.Random(20260111)
-    for w in WIDTHS:
+    def ops_at(w, rng):
         xs = _operands(w, rng)
         for a in xs:
             case(ir.W_NOT, w, 0, a, 0, O.bvnot(a, w))
@@ -116,6 +118,10 @@ def _cases():
                     if 1 <= wb < wr:
                         hi, lo = a & O.M(wr - wb), b & O.M(wb)
                         case(ir.W_CONCAT, wr, wb, hi, lo, O.concat(hi, lo, wb))
+
+    rng = random.Random(20260111)
+    for w in WIDTHS:
+        ops_at(w, rng)
     n_ops = len(out) - n_golden
 
     # the multi-digit division (Knuth's algorithm D), which the vectors above barely reach
@@ -147,7 +153,22 @@ def _cases():
     # an opcode that is no function of two values is reported, not evaluated
     for op in (ir.W_ITE, ir.W_VAR, ir.B_AND, ir.END):
         out.append((f"{op:x} 100 0 1 1", "?"))
-    return out, n_golden, n_ops
+
+    # every width 1..256: the op-by-op section at the widths it has not run at above, then every
+    # arithmetic op and compare on the width catalogue's 8-row lists (tests/width_cases.py, whose
+    # expectations are Python integers: test_width_cases.py holds them against the oracle's)
+    n_before = len(out)
+    rng = random.Random(20260116)
+    for w in range(1, 257):
+        if w not in WIDTHS:
+            ops_at(w, rng)
+    n_wide = len(out) - n_before
+    for key in WC.GROUND_KEYS:
+        op = WC.BIN[key] if key in WC.BIN else WC.CMP[key]
+        for w in WC.WIDTHS:
+            for r in WC.rows(key, w, WC.N_SEARCH):
+                case(op, w, 0, r.args[0], r.args[1], r.expect)
+    return out, n_golden, n_ops, (n_wide, len(out) - n_before - n_wide)
 
 
 def test_shared_evaluator_against_golden_vectors_and_the_oracle(tmp_path):
@@ -158,10 +179,14 @@ def test_shared_evaluator_against_golden_vectors_and_the_oracle(tmp_path):
     subprocess.run([gxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-static-libasan", "-static-libubsan",
                     "-o", exe, os.path.join(ROOT, "tests", "host_ops_check.cpp")], check=True)
-    cases, n_golden, n_ops = _cases()
+    cases, n_golden, n_ops, (n_wide, n_catalogue) = _cases()
     assert n_golden == 10152 and n_ops > 5 * 9 * 10
     # the division, EXP and MUL cases and the 5 + 4 requests after them
-    assert len(cases) - n_golden - n_ops == 3 * 12 * 5 + 2 * 2000 + 5 * 8 * 8 + 9 * 9 + 9
+    assert len(cases) - n_golden - n_ops - n_wide - n_catalogue == 3 * 12 * 5 + 2 * 2000 + 5 * 8 * 8 + 9 * 9 + 9
+    # 251 more widths of the op-by-op section (at least what its smallest width gives), and
+    # 15 ops + 7 compares x 256 widths x 8 rows
+    assert n_wide > 251 * 9 * 10 and n_wide * 5 > n_ops * 251 // 2
+    assert n_catalogue == 22 * 256 * 8
     p = subprocess.run([exe], input="".join(q + "\n" for q, _ in cases), capture_output=True, text=True)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     got = p.stdout.split("\n")

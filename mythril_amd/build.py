@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpathfeas.so")
-SOURCES = ["pathfeas.hip", "pf_eval.hip", "pf_keccak.hip", "pf_devprog.h", "pf_fold.h", "pf_hostint.h", "u256.h", "u256_cols.h",
+SOURCES = ["pathfeas.hip", "pf_eval.hip", "pf_keccak.hip", "pf_devprog.h", "pf_launch.h", "pf_fold.h", "pf_hostint.h", "u256.h", "u256_cols.h",
            os.path.join("..", "..", "include", "pathfeas.h"),
            os.path.join("..", "..", "include", "pf_bytecode.h")]
 

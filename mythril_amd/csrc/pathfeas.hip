@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -19,6 +20,7 @@
 
 #include "../../include/pathfeas.h"
 #include "pf_devprog.h"
+#include "pf_launch.h"
 #include "pf_eval.hip"
 #include "pf_keccak.hip"
 
@@ -26,6 +28,8 @@ namespace {
 
 // the host half — validator, device-program rewrites, threaded preparation, wave order
 using namespace pf_devprog;
+// request checks, launch orders, launch geometry, the counter sum, al()
+using namespace pf_launch;
 
 std::mutex g_mu;
 thread_local std::string g_err_tls;
@@ -71,12 +75,9 @@ int g_default = -1;       // index in g_devs of the default device (lowest id)
 // the full sweep peaks at 512 (finer slices even out the sets' unequal costs in the last round
 // of waves; 64 was 17 % slower).  The early-exit search is a work queue of (set, chunk) items
 // taken by a chip-filling grid: 16 waves per CU (4 per SIMD, the narrow kernels' occupancy;
-// PF_WAVES_PER_CU_EARLY), chunks of g_early_chunk_groups 64-candidate groups
+// PF_WAVES_PER_CU_EARLY), chunks of early_chunk_groups 64-candidate groups
 // (PF_EARLY_CHUNK_GROUPS).
-uint32_t g_waves_per_cu_full = 512;
-uint32_t g_waves_per_cu_early = 16;
-uint32_t g_early_chunk_groups = 8;
-// Early-exit searches of 2 .. g_probe_max_sets sets that all carry a parent / hint model
+// Early-exit searches of 2 .. probe_max_sets sets that all carry a parent / hint model
 // (candidate 0) start with a probe launch: one wave per set evaluates only candidates 0..63,
 // then the queue search runs behind it on the stream from candidate 64 and skips every set the
 // probe decided.  Without it every wave of the chip-filling grid claims its item before any
@@ -91,7 +92,9 @@ uint32_t g_early_chunk_groups = 8;
 // caller's PF_FLAG_NO_PROBE skips the probe when it knows a set's candidate 0 misses (check_sets:
 // a host hint model that leaves a root false — the probe of a long program then only delays
 // the search behind it; profiles/r06_probe_rule.md).
-uint32_t g_probe_max_sets = 64;
+// pf_launch.h has the defaults and the rules (geometry, probe_first), which take the knobs as an
+// argument; read_env_knobs overrides them.
+Knobs g_knobs;
 // PF_DEVICE_FOLD as read at init (pf_devprog.h device_fold_env): what pf_batch_create folds with
 int g_device_fold = 1;
 
@@ -105,18 +108,34 @@ int fail(const char* fmt, ...) {
     return -1;
 }
 
+// the header's checks return their message: empty is no error
+bool failed(const std::string& e) {
+    if (!e.empty()) g_err = e;
+    return !e.empty();
+}
+
 #define HIPCHK(x)                                                                       \
     do {                                                                                \
         hipError_t e_ = (x);                                                            \
         if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), \
                                           __FILE__, __LINE__);                          \
     } while (0)
+// inside a pooled round trip (Pooled): the entry point's own message
+#define HIPTRY(who, x)                                                  \
+    do {                                                                \
+        if ((x) != hipSuccess) return fail("%s: HIP call failed", who); \
+    } while (0)
+
+// A batch's device blocks.  The main block holds the arrays pf_batch_create uploads; each of the
+// others is acquired by the batch's first call of its entry point (ensure) and lives as long as
+// the batch.
+enum Side { kMain, kClimb, kCensus, kStream, kLink, kSides };
+struct Block { void* mem = nullptr; size_t cap = 0; };
 
 struct Batch {
     int device;
-    void* d_mem = nullptr;  // one device block holding every array below
-    size_t mem_cap = 0;
-    size_t n_ins, n_const, n_vars, n_parents, n_sets;
+    Block side[kSides];
+    size_t n_vars, n_sets;
     uint32_t max_vars;
     size_t n_narrow = 0;    // d_order[0, n_narrow): sets whose programs write only W registers
                             // < PF_NW_NARROW (8-register kernels, 3 waves/SIMD); the rest run
@@ -134,50 +153,41 @@ struct Batch {
     uint32_t* d_scratch = nullptr;  // this batch's t0 (u64 [4]), queue heads and counter lines (pf_bytecode.h)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // climb (pf_climb_batch): per set, whether it runs the 16-register kernels and the assert
-    // sites of its device program; the climb block — working descriptors and schema (every
-    // variable parented), the two parent buffers, the per-set states — is allocated by the
-    // batch's first climb and lives as long as the batch
+    // sites of its device program; the climb block holds working descriptors and schema (every
+    // variable parented), the two parent buffers and the per-set states
     std::vector<uint8_t> h_wide;
     std::vector<uint32_t> h_sites;
-    void* c_mem = nullptr;
-    size_t c_cap = 0;
-    // census (pf_census_batch): the census block — per-set states, the rows holds / alive / sole
-    // of every set, this call's tables — is allocated by the batch's first census and lives as
-    // long as the batch
-    void* s_mem = nullptr;
-    size_t s_cap = 0;
+    // census (pf_census_batch): the census block holds per-set states, the rows holds / alive /
+    // sole of every set and this call's tables
     // stream (pf_eval_batch): d_order's host copy, and the stream block — a call's sets in launch
-    // order and their places in the request, n_sets u32 each — allocated by the batch's first
-    // stream call; e_req is what the block holds (a call with the same request uploads nothing)
+    // order and their places in the request, n_sets u32 each; e_req is what the block holds (a
+    // call with the same request uploads nothing)
     std::vector<uint32_t> h_order;
-    void* e_mem = nullptr;
-    size_t e_cap = 0;
     std::vector<uint32_t> e_req;
     // linked search (pf_check_linked): host copies of what a link group's members share, and
     // the link block — this call's group of every set and members of every group, the groups'
-    // verdicts, one (mask, count) record per group and 64 candidates — allocated by the batch's
-    // first linked call, grown when a later call needs more; l_req is the group_of it holds
+    // verdicts, one (mask, count) record per group and 64 candidates — the one block whose size
+    // depends on the call: grown when a later call needs more; l_req is the group_of it holds
     LinkTables h_link;
-    void* l_mem = nullptr;
-    size_t l_cap = 0;
     std::vector<uint32_t> l_req;
-    ~Batch() {  // the device block goes back to its device's pool first (release_batch)
-        if (d_mem) hipFree(d_mem);
-        if (c_mem) hipFree(c_mem);
-        if (s_mem) hipFree(s_mem);
-        if (e_mem) hipFree(e_mem);
-        if (l_mem) hipFree(l_mem);
+
+    // views of the scratch (pf_bytecode.h).  The kernels take the scratch's base for their
+    // counters and add PF_COUNTER_OFF themselves.
+    static constexpr size_t kT0Word = 8;  // t0 starts 32 bytes in
+    unsigned long long* counters() const { return reinterpret_cast<unsigned long long*>(d_scratch); }
+    uint64_t* t0() const { return reinterpret_cast<uint64_t*>(d_scratch + kT0Word); }
+    // the work-queue heads of one (phase, part) launch; climb, census and stream have one phase
+    uint32_t* queue(int phase, int part) const {
+        return d_scratch + PF_EARLY_QUEUE_OFF / 4 + (phase * 2 + part) * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;
+    }
+    const uint32_t* counter_lines() const { return d_scratch + PF_COUNTER_OFF / 4; }
+
+    ~Batch() {  // the device blocks go back to their device's pool first (release_batch)
+        for (Block& b : side)
+            if (b.mem) hipFree(b.mem);
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
     }
-};
-
-// Temporary device buffer freed on every return path (HIPCHK returns early).
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { hipFree(p); }
-    template <typename T>
-    T* as() { return static_cast<T*>(p); }
 };
 
 Dev* find_dev(int key) {
@@ -212,9 +222,8 @@ void* pool_acquire(Dev* D, size_t bytes, size_t* cap) {
     return p;
 }
 
-// free a batch: its block is kept for reuse (the oldest block is released when the pool is
-// full).  Called with no launch of the batch in flight (pf_batch_free drains the device).
-// a block back into its device's pool (the oldest block is released when the pool is full)
+// a block back into its device's pool (the oldest block is released when the pool is full).
+// Nothing that uses the block may be in flight.
 void pool_release(Dev* D, void* p, size_t cap) {
     std::lock_guard<std::mutex> pk(g_pool_mu);
     if (D->pool.size() >= kPoolBlocks) {
@@ -224,26 +233,57 @@ void pool_release(Dev* D, void* p, size_t cap) {
     D->pool.emplace_back(p, cap);
 }
 
+// A block that work still in flight may read or write (a copy or a synchronisation failed) is
+// not pooled again: it is freed after a full device synchronisation, whose own failure leaks it
+// rather than hand memory in use to the next pool_acquire.
+void free_in_flight(void* p) {
+    if (hipDeviceSynchronize() == hipSuccess) hipFree(p);
+}
+
+// One pooled block for a call's round trip: copy in, launch, copy out, stream synchronised.
+// release() hands it back to the pool once the stream is drained; a return before that (a failed
+// HIP call) leaves it to free_in_flight.
+struct Pooled {
+    Dev* D;
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    // in the body: pool_acquire writes cap, which a member initialiser would then reset
+    Pooled(Dev* D, size_t bytes) : D(D) { p = static_cast<uint8_t*>(pool_acquire(D, bytes, &cap)); }
+    Pooled(const Pooled&) = delete;
+    void release() {
+        pool_release(D, p, cap);
+        p = nullptr;
+    }
+    ~Pooled() {
+        if (p) free_in_flight(p);
+    }
+};
+
+// B's side block `kind` with room for `bytes`: acquired by the first call that needs it,
+// replaced when a call needs more (nothing of the batch is in flight: every earlier call on it
+// returned after its results).  *fresh: the block is new, whatever the caller remembers of its
+// contents is gone.
+int ensure(Dev* D, Batch* B, Side kind, size_t bytes, const char* who, bool* fresh = nullptr) {
+    Block& b = B->side[kind];
+    if (fresh) *fresh = !b.mem || b.cap < bytes;
+    if (b.mem && b.cap < bytes) {
+        pool_release(D, b.mem, b.cap);
+        b.mem = nullptr;
+    }
+    if (!b.mem) {
+        b.mem = pool_acquire(D, bytes, &b.cap);
+        if (!b.mem) return fail("%s: hipMalloc(%zu) failed", who, bytes);
+    }
+    return 0;
+}
+
+// free a batch: its blocks are kept for reuse.  Called with no launch of the batch in flight
+// (pf_batch_free drains the stream of the device's last launch).
 void release_batch(Dev* D, Batch* B) {
-    if (D && B->d_mem) {
-        pool_release(D, B->d_mem, B->mem_cap);
-        B->d_mem = nullptr;
-    }
-    if (D && B->c_mem) {
-        pool_release(D, B->c_mem, B->c_cap);
-        B->c_mem = nullptr;
-    }
-    if (D && B->s_mem) {
-        pool_release(D, B->s_mem, B->s_cap);
-        B->s_mem = nullptr;
-    }
-    if (D && B->e_mem) {
-        pool_release(D, B->e_mem, B->e_cap);
-        B->e_mem = nullptr;
-    }
-    if (D && B->l_mem) {
-        pool_release(D, B->l_mem, B->l_cap);
-        B->l_mem = nullptr;
+    for (Block& b : B->side) {
+        if (!D || !b.mem) continue;
+        pool_release(D, b.mem, b.cap);
+        b.mem = nullptr;
     }
     if (D) {
         std::lock_guard<std::mutex> pk(g_pool_mu);
@@ -296,38 +336,24 @@ Batch* as_batch(uint64_t h) { return reinterpret_cast<Batch*>(static_cast<uintpt
 
 hipStream_t pick_stream(Dev* D, void* s) { return s ? reinterpret_cast<hipStream_t>(s) : D->stream; }
 
-// launch geometry for the search kernel: enough waves to fill the CUs several times over,
-// each wave walking >= 64 candidates of one set.
-void geometry(int num_cus, uint32_t n_sets, uint32_t budget, uint32_t flags, uint32_t* per_wave,
-              uint32_t* slices) {
-    if (flags & PF_FLAG_EARLY_EXIT) {
-        // work-queue items: chunks of g_early_chunk_groups groups, larger when the batch
-        // would make more than 64 items per wave — every item costs a claim (an L2 atomic,
-        // ~14 ns per head) even when its set is already decided, which dominated planted
-        // batches of 65,536 sets (tools/full_pass.py: 136 ms per 1M sets at 8 groups)
-        const uint64_t groups = (budget + 63u) / 64u;
-        const uint64_t max_items = (uint64_t)num_cus * g_waves_per_cu_early * 64u;
-        uint64_t cg = std::max<uint64_t>(g_early_chunk_groups, (n_sets * groups + max_items - 1) / max_items);
-        // small batches (the funnel's single queries, fork pairs): chunks small enough that
-        // every wave slot of the grid gets an item, so a set without a witness among its
-        // candidates takes one chunk's time per wave, not g_early_chunk_groups groups'
-        const uint64_t slots = (uint64_t)num_cus * g_waves_per_cu_early;
-        const uint64_t fill = (n_sets * groups + slots - 1) / slots;
-        if (fill < cg) cg = fill;
-        cg = std::max<uint64_t>(1, std::min<uint64_t>(cg, groups));
-        *per_wave = (uint32_t)(cg * 64u);
-        *slices = std::max<uint32_t>(1u, (budget + *per_wave - 1) / *per_wave);
-        return;
-    }
-    const uint64_t target_waves =
-        (uint64_t)num_cus * ((flags & PF_FLAG_EARLY_EXIT) ? g_waves_per_cu_early : g_waves_per_cu_full);
-    uint64_t groups = (budget + 63u) / 64u;  // 64-candidate groups per set
-    uint64_t sl = (target_waves + n_sets - 1) / std::max<uint32_t>(n_sets, 1u);
-    sl = std::max<uint64_t>(1, std::min<uint64_t>(sl, groups));
-    uint64_t gpw = (groups + sl - 1) / sl;  // groups per wave
-    *per_wave = (uint32_t)(gpw * 64u);
-    *slices = (uint32_t)((budget + *per_wave - 1) / *per_wave);
-    if (*slices == 0) *slices = 1;
+// the search kernels by [early exit][16-register part]; the linked ones take the link block
+// where the others take found[]
+decltype(&pf_check_kernel) const kCheckKernels[2][2] = {{pf_check_kernel, pf_check_r16_kernel},
+                                                         {pf_check_early_kernel, pf_check_early_r16_kernel}};
+decltype(&pf_check_linked_kernel) const kLinkedKernels[2][2] = {
+    {pf_check_linked_kernel, pf_check_linked_r16_kernel},
+    {pf_check_linked_early_kernel, pf_check_linked_early_r16_kernel}};
+
+// What every launch sequence on a batch starts with: t0 and the profiling slots at the scratch's
+// front, the work-queue heads of every launch from PF_EARLY_QUEUE_OFF, the counter lines from
+// PF_COUNTER_OFF and the first nf words of found[] in one fill, then B's first event.
+int reset_scratch(Batch* B, hipStream_t st, uint32_t* d_found, uint32_t nf) {
+    const uint32_t nz = PF_SCRATCH_BYTES / 4;
+    const uint32_t blocks = std::min<uint32_t>((nz + nf + 255u) / 256u, 1024u);
+    hipLaunchKernelGGL(pf_reset_kernel, dim3(blocks), dim3(256), 0, st, B->d_scratch, nz, d_found, nf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B->ev0, st));
+    return 0;
 }
 
 // Enqueue one search over batch B on stream st (B's device must be current).  With `link` it is
@@ -336,17 +362,7 @@ void geometry(int num_cus, uint32_t n_sets, uint32_t budget, uint32_t flags, uin
 int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uint32_t timeout_ms,
                   uint32_t* d_found, hipStream_t st, const LinkArgs* link = nullptr, uint32_t n_link_groups = 0) {
     Dev* D = find_dev(B->device);
-    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
-    uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
-    // t0 and the profiling slots at the front, the work-queue heads of both launch parts from
-    // PF_EARLY_QUEUE_OFF, the counter lines from PF_COUNTER_OFF: one fill for all
-    {
-        const uint32_t nz = PF_SCRATCH_BYTES / 4, nf = link ? 0u : (uint32_t)std::max<size_t>(B->n_sets, 1);
-        const uint32_t blocks = std::min<uint32_t>((nz + nf + 255u) / 256u, 1024u);
-        hipLaunchKernelGGL(pf_reset_kernel, dim3(blocks), dim3(256), 0, st, B->d_scratch, nz, d_found, nf);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(B->ev0, st));
+    if (reset_scratch(B, st, d_found, link ? 0u : (uint32_t)std::max<size_t>(B->n_sets, 1))) return -1;
     if (link) {
         const uint64_t n_rec = (uint64_t)n_link_groups * link->words;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_rec + n_link_groups + 255u) / 256u, 1024u);
@@ -358,44 +374,30 @@ int check_enqueue(Batch* B, uint64_t gseed, uint32_t budget, uint32_t flags, uin
     const bool early = flags & PF_FLAG_EARLY_EXIT;
     // phase 0: the probe (early exit, small batches: candidates 0..63 of every set, one wave
     // per set); phase 1: the search over the whole budget, whose waves skip decided sets
-    const bool probe = early && budget > 64u && B->n_sets >= 2 && B->n_sets <= g_probe_max_sets &&
-                       B->all_parented && !(flags & PF_FLAG_NO_PROBE);
+    const bool probe = probe_first(g_knobs, B->n_sets, budget, flags, B->all_parented);
     for (int phase = probe ? 0 : 1; phase < 2; ++phase) {
-    const uint32_t pbudget = phase == 0 ? 64u : budget;
-    // the 8-register sets first, then the 16-register ones (usually none)
-    for (int part = 0; part < 2; ++part) {
-        const size_t first = part ? B->n_narrow : 0;
-        const size_t n = part ? B->n_sets - B->n_narrow : B->n_narrow;
-        if (n == 0 || budget == 0) continue;
-        uint32_t per_wave, slices;
-        // phase 1 after a probe: candidates 64.. only (the probe evaluated 0..63)
-        const uint32_t cbegin = (phase == 1 && probe) ? 64u : 0u;
-        geometry(D->num_cus, (uint32_t)n, pbudget - cbegin, flags, &per_wave, &slices);
-        const uint64_t items = (uint64_t)n * slices;
-        if (items > 0xffffffffull) return fail("batch too large: %llu waves", (unsigned long long)items);
-        // a chip-filling grid of persistent waves takes the items from the queue heads
-        // (zeroed above), in the full sweep as in the early-exit search
-        const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * (early ? g_waves_per_cu_early : 16u));
-        // each (phase, part) launch has its own heads, all zeroed by the reset above
-        uint32_t* d_queue =
-            B->d_scratch + PF_EARLY_QUEUE_OFF / 4 + (phase * 2 + part) * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;
-        const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
-        if (link)
-            hipLaunchKernelGGL(part == 0 ? (early ? pf_check_linked_early_kernel : pf_check_linked_kernel)
-                                         : (early ? pf_check_linked_early_r16_kernel : pf_check_linked_r16_kernel),
-                               dim3(blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, B->d_order + first,
-                               (uint32_t)n, B->d_code, B->d_consts, B->d_schema, B->d_parents,
-                               gseed, pbudget, per_wave, slices, flags, deadline, d_t0, *link, d_counters,
-                               d_queue, cbegin);
-        else
-        hipLaunchKernelGGL(part == 0 ? (early ? pf_check_early_kernel : pf_check_kernel)
-                                     : (early ? pf_check_early_r16_kernel : pf_check_r16_kernel),
-                           dim3(blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, B->d_order + first,
-                           (uint32_t)n, B->d_code, B->d_consts, B->d_schema, B->d_parents,
-                           gseed, pbudget, per_wave, slices, flags, deadline, d_t0, d_found, d_counters,
-                           d_queue, cbegin);
-        HIPCHK(hipGetLastError());
-    }
+        const uint32_t pbudget = phase == 0 ? 64u : budget;
+        // the 8-register sets first, then the 16-register ones (usually none)
+        for (int part = 0; part < 2; ++part) {
+            const size_t first = part ? B->n_narrow : 0;
+            const size_t n = part ? B->n_sets - B->n_narrow : B->n_narrow;
+            if (n == 0 || budget == 0) continue;
+            // phase 1 after a probe: candidates 64.. only (the probe evaluated 0..63)
+            const uint32_t cbegin = (phase == 1 && probe) ? 64u : 0u;
+            // a chip-filling grid of persistent waves takes the items from this launch's queue
+            // heads (each (phase, part) launch has its own, all zeroed by the reset above)
+            const Grid g = geometry(g_knobs, D->num_cus, (uint32_t)n, pbudget - cbegin, flags);
+            if (g.items > 0xffffffffull) return fail("batch too large: %llu waves", (unsigned long long)g.items);
+            auto launch = [&](auto kernel, auto verdicts) {
+                hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs,
+                                   B->d_order + first, (uint32_t)n, B->d_code, B->d_consts, B->d_schema, B->d_parents,
+                                   gseed, pbudget, g.per, g.slices, flags, deadline, B->t0(), verdicts, B->counters(),
+                                   B->queue(phase, part), cbegin);
+            };
+            if (link) launch(kLinkedKernels[early][part], *link);
+            else launch(kCheckKernels[early][part], d_found);
+            HIPCHK(hipGetLastError());
+        }
     }
     HIPCHK(hipEventRecord(B->ev1, st));
     return 0;
@@ -444,50 +446,84 @@ uint8_t* upload_staging(size_t bytes) {
     return p;
 }
 
-// Wait for B's last search on stream st and read its counters.
-// counters and kernel time of the last launch; with `found`, the verdicts too, copied before
-// the one stream synchronisation (a second round trip was ~4 % of a single query's search)
+// What the launches between B's events left, from the counter lines as read back (the caller
+// copies them with its own results and synchronises once): the lines summed, the events' time.
+// The entry points differ in what their kernels count:
+enum StatsOf {
+    kSearchStats,  // n_sat is the caller's; ops and timeouts are counted
+    kSideStats,    // climb, census: the same without ops
+    kStreamStats   // n_sat is the lines' slot 4 (the sets with a witness), no ops, no timeouts
+};
+int fill_stats(Batch* B, const unsigned long long* lines, StatsOf of, uint64_t n_sat, pf_stats* stats) {
+    unsigned long long h[5];
+    sum_counters(lines, h);
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
+    stats->evals_full = h[0];
+    stats->cands_decided = h[1];
+    stats->ops = of == kSearchStats ? h[2] : 0;
+    stats->n_sat = of == kStreamStats ? h[4] : n_sat;
+    stats->kernel_ms = ms;
+    stats->timed_out = of != kStreamStats && h[3] ? 1u : 0u;
+    return 0;
+}
+
+// Wait for B's last search or stream call on stream st and read its counters and kernel time;
+// with `found`, the verdicts too, copied before the one stream synchronisation (a second round
+// trip was ~4 % of a single query's search).  A search's n_sat is left 0 for the caller
+// (found_to_host).
 // (d_from, n_from): the verdicts' device buffer and count when they are not the batch's found[]
 // (the linked search's group verdicts)
-int check_collect(Batch* B, hipStream_t st, pf_stats* stats, std::vector<uint32_t>* found = nullptr,
+int check_collect(Batch* B, hipStream_t st, StatsOf of, pf_stats* stats, std::vector<uint32_t>* found = nullptr,
                   const uint32_t* d_from = nullptr, size_t n_from = 0) {
-    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
     const size_t nf = d_from ? n_from : std::max<size_t>(B->n_sets, 1);
     if (!d_from) d_from = B->d_found;
-    unsigned long long hs[PF_COUNTER_STRIPES * 16];
-    uint8_t* pin = pinned_staging(cbytes + (found ? nf * 4 : 0));
-    const uint32_t* d_counters = B->d_scratch + PF_COUNTER_OFF / 4;
+    unsigned long long hs[kCounterBytes / 8];
+    uint8_t* pin = pinned_staging(kCounterBytes + (found ? nf * 4 : 0));
+    const uint32_t* d_lines = B->counter_lines();
     if (found) found->assign(nf, 0u);
-    if (found && pin && d_from == d_counters + cbytes / 4) {
+    if (found && pin && d_from == d_lines + kCounterBytes / 4) {
         // the batch block keeps found[] right after the counter lines: one copy (each copy is
         // a blit dispatch serialised behind the search)
-        HIPCHK(hipMemcpyAsync(pin, d_counters, cbytes + nf * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(pin, d_lines, kCounterBytes + nf * 4, hipMemcpyDeviceToHost, st));
     } else {
-        HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(hs), d_counters, cbytes,
+        HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(hs), d_lines, kCounterBytes,
                               hipMemcpyDeviceToHost, st));
         if (found)
-            HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin + cbytes) : static_cast<void*>(found->data()),
+            HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin + kCounterBytes) : static_cast<void*>(found->data()),
                                   d_from, nf * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     if (pin) {
-        memcpy(hs, pin, cbytes);
-        if (found) memcpy(found->data(), pin + cbytes, nf * 4);
+        memcpy(hs, pin, kCounterBytes);
+        if (found) memcpy(found->data(), pin + kCounterBytes, nf * 4);
     }
-    unsigned long long h[4] = {0, 0, 0, 0};
-    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
-        for (int k = 0; k < 4; k++) h[k] += hs[i * 16 + k];
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
-    if (stats) {
-        stats->evals_full = h[0];
-        stats->cands_decided = h[1];
-        stats->ops = h[2];
-        stats->kernel_ms = ms;
-        stats->n_sat = 0;
-        stats->timed_out = h[3] ? 1u : 0u;
+    pf_stats unused;
+    return fill_stats(B, hs, of, 0, stats ? stats : &unused);
+}
+
+// The two copies of a pooled round trip.  With the pinned staging buffer (pin) each is one copy
+// through it: no pageable copies, which are staged and synchronous in the runtime.  Without
+// (pin null: its allocation failed) they go straight from and to the caller's memory.
+struct Piece { size_t off; const void* src; size_t bytes; };  // off: in the block and in the staging buffer
+// in: the pieces to dm + off — staged, one copy of [0, the last piece's end)
+hipError_t copy_in(uint8_t* dm, uint8_t* pin, std::initializer_list<Piece> pieces, hipStream_t st) {
+    size_t end = 0;
+    for (const Piece& c : pieces) {
+        end = c.off + c.bytes;
+        if (!c.bytes) continue;
+        if (pin) memcpy(pin + c.off, c.src, c.bytes);
+        else if (hipError_t e = hipMemcpyAsync(dm + c.off, c.src, c.bytes, hipMemcpyHostToDevice, st)) return e;
     }
-    return 0;
+    return pin ? hipMemcpyAsync(dm, pin, end, hipMemcpyHostToDevice, st) : hipSuccess;
+}
+// out: `bytes` at d to `out`, and the stream drained.  The staging buffer is reused: the stream
+// orders this copy after the launch, which has consumed the copy-in.
+hipError_t copy_out(void* out, const uint8_t* d, size_t bytes, uint8_t* pin, hipStream_t st) {
+    if (hipError_t e = hipMemcpyAsync(pin ? static_cast<void*>(pin) : out, d, bytes, hipMemcpyDeviceToHost, st)) return e;
+    if (hipError_t e = hipStreamSynchronize(st)) return e;
+    if (pin) memcpy(out, pin, bytes);
+    return hipSuccess;
 }
 
 }  // namespace
@@ -600,19 +636,19 @@ void read_env_knobs() {
     g_device_fold = device_fold_env();
     if (const char* e = getenv("PF_WAVES_PER_CU")) {
         long v = strtol(e, nullptr, 10);
-        if (v >= 8 && v <= 4096) g_waves_per_cu_full = g_waves_per_cu_early = (uint32_t)v;
+        if (v >= 8 && v <= 4096) g_knobs.waves_per_cu_full = g_knobs.waves_per_cu_early = (uint32_t)v;
     }
     if (const char* e = getenv("PF_WAVES_PER_CU_EARLY")) {  // the early-exit search alone
         long v = strtol(e, nullptr, 10);
-        if (v >= 1 && v <= 4096) g_waves_per_cu_early = (uint32_t)v;
+        if (v >= 1 && v <= 4096) g_knobs.waves_per_cu_early = (uint32_t)v;
     }
     if (const char* e = getenv("PF_PROBE_MAX_SETS")) {
         long v = strtol(e, nullptr, 10);
-        if (v >= 0) g_probe_max_sets = (uint32_t)v;
+        if (v >= 0) g_knobs.probe_max_sets = (uint32_t)v;
     }
     if (const char* e = getenv("PF_EARLY_CHUNK_GROUPS")) {
         long v = strtol(e, nullptr, 10);
-        if (v >= 1 && v <= 1024) g_early_chunk_groups = (uint32_t)v;
+        if (v >= 1 && v <= 1024) g_knobs.early_chunk_groups = (uint32_t)v;
     }
 }
 
@@ -726,7 +762,6 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
     // constant pool: the generator's constant gather is issued before it knows whether the
     // set has constants (pf_eval.hip gen_var), so a set with none reads the entry at its own
     // const_off, which may be the pool's end.
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     // the code region carries one zero instruction past the last END: the kernel fetches the
     // slot after an END before its dispatch leaves the program (pf_eval.hip run_program)
     const size_t o_code = 0, o_const = o_code + al(n_ins * 16 + 16), o_schema = o_const + al(n_const * 32 + 32),
@@ -767,10 +802,7 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         if (!handle_out) return set_err("pf_batch_create: null handle_out");
         B = new Batch();
         B->device = Dv->key;
-        B->n_ins = n_ins;
-        B->n_const = n_const;
         B->n_vars = n_vars;
-        B->n_parents = n_parents;
         B->n_sets = n_sets;
         B->max_vars = pp.max_vars;
         B->n_narrow = (size_t)std::count(pp.wide.begin(), pp.wide.end(), (uint8_t)0);
@@ -786,12 +818,13 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         if (n_const && consts) B->h_link.consts.assign(consts, consts + 8 * n_const);
         if (n_vars && schema) B->h_link.schema.assign(schema, schema + 4 * n_vars);
         if (n_parents && parents) B->h_link.parents.assign(parents, parents + 8 * n_parents);
-        B->d_mem = pool_acquire(Dv, total, &B->mem_cap);
-        if (!B->d_mem) {
+        Block& main = B->side[kMain];
+        main.mem = pool_acquire(Dv, total, &main.cap);
+        if (!main.mem) {
             delete B;
             return set_err(errorf("pf_batch_create: hipMalloc(%zu) failed", total));
         }
-        uint8_t* base = static_cast<uint8_t*>(B->d_mem);
+        uint8_t* base = static_cast<uint8_t*>(main.mem);
         B->d_code = reinterpret_cast<uint4*>(base + o_code);
         B->d_consts = reinterpret_cast<uint32_t*>(base + o_const);
         B->d_schema = reinterpret_cast<uint4*>(base + o_schema);
@@ -816,19 +849,18 @@ int pf_batch_create_on(int device, const uint32_t* code, size_t n_ins, const uin
         uint8_t* pin = ok ? upload_staging(o_scr) : nullptr;
         if (pin) {
             fill(pin);
-            ok = hipMemcpyAsync(B->d_mem, pin, o_scr, hipMemcpyHostToDevice, ups) == hipSuccess &&
+            ok = hipMemcpyAsync(B->side[kMain].mem, pin, o_scr, hipMemcpyHostToDevice, ups) == hipSuccess &&
                  hipStreamSynchronize(ups) == hipSuccess;
         } else if (ok) {
             std::vector<uint8_t> stage(o_scr);
             fill(stage.data());
-            ok = hipMemcpy(B->d_mem, stage.data(), o_scr, hipMemcpyHostToDevice) == hipSuccess;
+            ok = hipMemcpy(B->side[kMain].mem, stage.data(), o_scr, hipMemcpyHostToDevice) == hipSuccess;
         }
     }
     if (!ok) {
-        // the copy may still be in flight: drain the device and free the block rather than
-        // pool it (the next pool_acquire would hand out memory still being written)
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(B->d_mem);
-        B->d_mem = nullptr;
+        // the copy may still be in flight: the block is not pooled
+        free_in_flight(B->side[kMain].mem);
+        B->side[kMain].mem = nullptr;
         delete B;
         return set_err(errorf("pf_batch_create: hipMemcpy of %zu bytes failed", o_scr));
     }
@@ -885,7 +917,7 @@ int pf_check_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint3
     if (!D || switch_stream(D, D->stream)) return -1;
     if (check_enqueue(B, global_seed, budget, flags, timeout_ms, B->d_found, D->stream)) return -1;
     std::vector<uint32_t> found;
-    if (check_collect(B, D->stream, stats, &found)) return -1;
+    if (check_collect(B, D->stream, kSearchStats, stats, &found)) return -1;
     return found_to_host(B, found, found_out, sat_bitmap_out, stats);
 }
 
@@ -899,34 +931,22 @@ int pf_check_linked(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
     if (!found_out) return fail("pf_check_linked: null found_out");
     if (B->n_sets == 0) return fail("pf_check_linked: the batch has no sets");
     std::vector<uint32_t> parts;
-    {
-        const std::string e = link_validate(B->h_descs, B->h_link, group_of, n_groups, parts);
-        if (!e.empty()) return fail("%s", e.c_str());
-    }
+    if (failed(link_validate(B->h_descs, B->h_link, group_of, n_groups, parts))) return -1;
     const size_t ns = B->n_sets;
-    const uint32_t words = (uint32_t)(((uint64_t)budget + 63u) / 64u);
+    const uint32_t words = groups_of(budget);
     Dev* D = use_dev(B->device);
     if (!D || switch_stream(D, D->stream)) return -1;
     hipStream_t st = D->stream;
     // the link block: [group_of: n_sets | parts: n_groups | found: n_groups | count: records | mask:
     // records], records = n_groups x ceil(budget / 64); sized to the call, grown when one needs more
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t n_rec = (size_t)n_groups * words;
     const size_t o_of = 0, o_parts = o_of + al(ns * 4), o_found = o_parts + al((size_t)n_groups * 4),
                  o_count = o_found + al((size_t)n_groups * 4), o_mask = o_count + al(n_rec * 4),
                  total = o_mask + al(n_rec * 8);
-    if (B->l_mem && B->l_cap < total) {
-        // nothing of this batch is in flight: every earlier call on it returned after its results
-        pool_release(D, B->l_mem, B->l_cap);
-        B->l_mem = nullptr;
-        B->l_req.clear();
-    }
-    if (!B->l_mem) {
-        B->l_mem = pool_acquire(D, total, &B->l_cap);
-        if (!B->l_mem) return fail("pf_check_linked: hipMalloc(%zu) failed", total);
-        B->l_req.clear();
-    }
-    uint8_t* lb = static_cast<uint8_t*>(B->l_mem);
+    bool fresh = false;
+    if (ensure(D, B, kLink, total, "pf_check_linked", &fresh)) return -1;
+    if (fresh) B->l_req.clear();
+    uint8_t* lb = static_cast<uint8_t*>(B->side[kLink].mem);
     LinkArgs L;
     L.group_of = reinterpret_cast<uint32_t*>(lb + o_of);
     L.parts = reinterpret_cast<uint32_t*>(lb + o_parts);
@@ -942,7 +962,7 @@ int pf_check_linked(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
         const size_t in_bytes = o_parts + (size_t)n_groups * 4;
         // sized for the results too: check_collect must not replace the buffer under this copy
         // (the stream orders its copies back after the upload has been consumed)
-        const size_t out_bytes = PF_COUNTER_STRIPES * 128 + (size_t)n_groups * 4;
+        const size_t out_bytes = kCounterBytes + (size_t)n_groups * 4;
         uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
         if (!pin) return fail("pf_check_linked: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
         memcpy(pin + o_of, group_of, ns * 4);
@@ -953,7 +973,7 @@ int pf_check_linked(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
     if (check_enqueue(B, global_seed, budget, flags, timeout_ms, nullptr, st, &L, n_groups)) return -1;
     std::vector<uint32_t> found;
     pf_stats local;
-    if (check_collect(B, st, &local, &found, L.found, n_groups)) return -1;
+    if (check_collect(B, st, kSearchStats, &local, &found, L.found, n_groups)) return -1;
     uint64_t n_sat = 0;
     for (uint32_t g = 0; g < n_groups; g++) {
         found_out[g] = found[g];
@@ -983,7 +1003,7 @@ int pf_check_batches(const uint64_t* handles, size_t n, uint64_t global_seed, ui
         if (!D) return -1;
         pf_stats* st = stats ? stats + i : nullptr;
         std::vector<uint32_t> found;
-        if (check_collect(B, D->stream, st, &found)) return -1;
+        if (check_collect(B, D->stream, kSearchStats, st, &found)) return -1;
         if (found_to_host(B, found, found_out ? found_out + off : nullptr, nullptr, st)) return -1;
         off += B->n_sets;
     }
@@ -1001,7 +1021,7 @@ int pf_check_batch_dev(uint64_t handle, uint64_t global_seed, uint32_t budget, u
     hipStream_t st = pick_stream(D, stream);
     if (switch_stream(D, st)) return -1;
     if (check_enqueue(B, global_seed, budget, flags, timeout_ms, d_found, st)) return -1;
-    return stats ? check_collect(B, st, stats) : 0;
+    return stats ? check_collect(B, st, kSearchStats, stats) : 0;
 }
 
 int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_ids,
@@ -1026,49 +1046,23 @@ int pf_materialize(uint64_t handle, uint64_t global_seed, const uint32_t* set_id
     // 256-byte aligned) and the pinned staging buffer for both copies: no hipMalloc / hipFree
     // (hipFree synchronises the device) and no pageable copies per call — this runs once per
     // funnel query whose witness is not a parented candidate 0
-    const size_t o_in = ((3 * n * 4) + 255) & ~size_t(255), bytes = o_in + total * 32;
-    size_t cap = 0;
-    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, bytes, &cap));
+    const size_t o_in = al(3 * n * 4), bytes = o_in + total * 32;
+    Pooled blk(D, bytes);
+    uint8_t* dm = blk.p;
     if (!dm) return fail("pf_materialize: hipMalloc(%zu) failed", bytes);
     uint32_t *d_sets = reinterpret_cast<uint32_t*>(dm), *d_cands = d_sets + n, *d_off = d_cands + n,
              *d_out = reinterpret_cast<uint32_t*>(dm + o_in);
     uint8_t* pin = pinned_staging(std::max<size_t>(3 * n * 4, total * 32));
-    int rc = 0;
-    if (pin) {
-        memcpy(pin, set_ids, n * 4);
-        memcpy(pin + n * 4, cand_ids, n * 4);
-        memcpy(pin + 2 * n * 4, off.data(), n * 4);
-        if (hipMemcpyAsync(d_sets, pin, 3 * n * 4, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
-    } else if (hipMemcpyAsync(d_sets, set_ids, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-               hipMemcpyAsync(d_cands, cand_ids, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-               hipMemcpyAsync(d_off, off.data(), n * 4, hipMemcpyHostToDevice, st) != hipSuccess) {
-        rc = -1;
-    }
-    if (!rc) {
-        const uint32_t mv = std::max<uint32_t>(B->max_vars, 1u);
-        const uint64_t threads = (uint64_t)n * mv;
-        hipLaunchKernelGGL(pf_materialize_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0,
-                           st, B->d_descs, B->d_code, B->d_consts, B->d_schema, B->d_parents,
-                           global_seed, d_sets, d_cands, d_off, (uint32_t)n, mv, d_out);
-        // the staging buffer is reused for the values: the stream orders the copies after the
-        // kernel, which has consumed the index copy
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(values_out), d_out, total * 32,
-                           hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            rc = -1;
-    }
-    if (!rc && pin) memcpy(values_out, pin, total * 32);
-    if (rc) {
-        // a failed copy or synchronisation after the copy-in may leave work on the stream
-        // that still reads or writes the block: it is not pooled again — freed
-        // after a full device synchronisation (whose own failure leaks it rather than hand
-        // memory in use to the next pool_acquire)
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
-        return fail("pf_materialize: HIP call failed");
-    }
-    // back to the pool (the stream is drained)
-    pool_release(D, dm, cap);
+    HIPTRY("pf_materialize",
+           copy_in(dm, pin, {{0, set_ids, n * 4}, {n * 4, cand_ids, n * 4}, {2 * n * 4, off.data(), n * 4}}, st));
+    const uint32_t mv = std::max<uint32_t>(B->max_vars, 1u);
+    const uint64_t threads = (uint64_t)n * mv;
+    hipLaunchKernelGGL(pf_materialize_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, st, B->d_descs,
+                       B->d_code, B->d_consts, B->d_schema, B->d_parents, global_seed, d_sets, d_cands, d_off,
+                       (uint32_t)n, mv, d_out);
+    HIPTRY("pf_materialize", hipGetLastError());
+    HIPTRY("pf_materialize", copy_out(values_out, dm + o_in, total * 32, pin, st));
+    blk.release();
     return 0;
 }
 
@@ -1090,20 +1084,12 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
         return fail("pf_climb_batch: unknown score %u", score);
     if (rounds == 0) return fail("pf_climb_batch: rounds must be at least 1");
     if (per_round == 0) return fail("pf_climb_batch: per_round must be at least 1");
-    if (n && !set_ids) return fail("pf_climb_batch: null set_ids");
     const size_t ns = B->n_sets;
-    {
-        std::vector<uint8_t> seen(ns, 0);
-        for (size_t i = 0; i < n; i++) {
-            if (set_ids[i] >= ns) return fail("pf_climb_batch: set %u out of range (%zu sets)", set_ids[i], ns);
-            if (seen[set_ids[i]]) return fail("pf_climb_batch: set %u requested twice", set_ids[i]);
-            seen[set_ids[i]] = 1;
-        }
-    }
+    if (failed(check_request("pf_climb_batch", ns, set_ids, n))) return -1;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return 0;
-    const uint32_t groups = (uint32_t)(((uint64_t)per_round + 63u) / 64u);
-    if ((uint64_t)n * groups > 0xffffffffull) return fail("pf_climb_batch: %zu sets x %u groups is too many items", n, groups);
+    const uint32_t groups = groups_of(per_round);
+    if (failed(check_items("pf_climb_batch", n, groups))) return -1;
     Dev* D = use_dev(B->device);
     if (!D) return -1;
     hipStream_t st = D->stream;
@@ -1118,15 +1104,11 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
         n_wvars += B->h_descs[s].n_vars;
     }
     if (n_wvars > 0xffffffffull / 8) return fail("pf_climb_batch: %zu variables", n_wvars);
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t o_wd = 0, o_ws = o_wd + al(ns * sizeof(pf_set_desc)), o_p0 = o_ws + al(n_wvars * 16 + 16),
                  o_p1 = o_p0 + al(n_wvars * 32 + 32), o_st = o_p1 + al(n_wvars * 32 + 32),
                  o_tab = o_st + al(ns * sizeof(pf_climb_set)), total = o_tab + al(3 * ns * 4);
-    if (!B->c_mem) {
-        B->c_mem = pool_acquire(D, total, &B->c_cap);
-        if (!B->c_mem) return fail("pf_climb_batch: hipMalloc(%zu) failed", total);
-    }
-    uint8_t* cb = static_cast<uint8_t*>(B->c_mem);
+    if (ensure(D, B, kClimb, total, "pf_climb_batch")) return -1;
+    uint8_t* cb = static_cast<uint8_t*>(B->side[kClimb].mem);
     pf_set_desc* d_wdescs = reinterpret_cast<pf_set_desc*>(cb + o_wd);
     uint4* d_wschema = reinterpret_cast<uint4*>(cb + o_ws);
     uint32_t* d_par[2] = {reinterpret_cast<uint32_t*>(cb + o_p0), reinterpret_cast<uint32_t*>(cb + o_p1)};
@@ -1136,15 +1118,11 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
 
     // this call's sets in launch order: the 8-register ones, then the 16-register ones
     std::vector<uint32_t> req;
-    req.reserve(n);
-    for (int part = 0; part < 2; ++part)
-        for (size_t i = 0; i < n; i++)
-            if ((int)B->h_wide[set_ids[i]] == part) req.push_back(set_ids[i]);
-    const size_t n_narrow = (size_t)std::count_if(req.begin(), req.end(), [&](uint32_t s) { return !B->h_wide[s]; });
+    const size_t n_narrow = request_order(B->h_wide, set_ids, n, req);
     std::vector<uint32_t> target(ns);
     for (size_t s = 0; s < ns; s++) target[s] = PF_CLIMB_HOLDS * B->h_sites[s];
 
-    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
+    constexpr size_t cbytes = kCounterBytes;
     const size_t in_bytes = 3 * ns * 4, out_bytes = cbytes + ns * sizeof(pf_climb_set) + n_wvars * 32;
     uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
     if (!pin) return fail("pf_climb_batch: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
@@ -1154,14 +1132,8 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
     memcpy(pin + 2 * ns * 4, req.data(), n * 4);
     HIPCHK(hipMemcpyAsync(d_wvoff, pin, in_bytes, hipMemcpyHostToDevice, st));
 
-    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
-    uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
-    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
     constexpr uint32_t n_queue = 2 * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE;  // the heads of both parts
-    hipLaunchKernelGGL(pf_reset_kernel, dim3((PF_SCRATCH_BYTES / 4 + 255u) / 256u), dim3(256), 0, st, B->d_scratch,
-                       (uint32_t)(PF_SCRATCH_BYTES / 4), B->d_found, 0u);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(B->ev0, st));
+    if (reset_scratch(B, st, B->d_found, 0u)) return -1;  // found[] is left alone
     hipLaunchKernelGGL(pf_climb_init_kernel, dim3((uint32_t)n), dim3(64), 0, st, B->d_descs, B->d_schema, d_req,
                        d_wvoff, d_target, d_wdescs, d_wschema, d_state);
     HIPCHK(hipGetLastError());
@@ -1175,37 +1147,31 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
         for (int part = 0; part < 2; ++part) {
             const size_t first = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
             if (np == 0) continue;
-            const uint64_t items = (uint64_t)np * groups;
-            const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early);
-            const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
+            const Grid g = group_grid(g_knobs, D->num_cus, np, groups);
             const auto kernel = score == PF_CLIMB_SCORE_TREE ? (part == 0 ? pf_climb_tree_kernel : pf_climb_tree_r16_kernel)
                                                              : (part == 0 ? pf_climb_kernel : pf_climb_r16_kernel);
-            hipLaunchKernelGGL(kernel, dim3(blocks),
-                               dim3(64 * PF_SEARCH_WG_WAVES), 0, st, descs_r, d_req + first, (uint32_t)np, B->d_code,
-                               B->d_consts, schema_r, parents_r, gs, per_round, groups, r ? 1u : 0u, deadline, d_t0,
-                               d_state, d_counters, d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+            hipLaunchKernelGGL(kernel, dim3(g.blocks), dim3(64 * PF_SEARCH_WG_WAVES), 0, st, descs_r, d_req + first,
+                               (uint32_t)np, B->d_code, B->d_consts, schema_r, parents_r, gs, per_round, groups,
+                               r ? 1u : 0u, deadline, B->t0(), d_state, B->counters(), B->queue(0, part));
             HIPCHK(hipGetLastError());
         }
+        // the adopt kernel clears the heads for the next round: the first part's, n_queue words on
         hipLaunchKernelGGL(pf_climb_adopt_kernel, dim3((uint32_t)n), dim3(64), 0, st, descs_r, d_wdescs, d_req,
                            B->d_code, B->d_consts, schema_r, parents_r, gs, r, d_par[r & 1u], d_par[(r + 1u) & 1u],
-                           d_state, d_queue, n_queue);
+                           d_state, B->queue(0, 0), n_queue);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(B->ev1, st));
     // counters, states and the final assignments (A_R, in buffer R & 1) in the staging buffer;
     // the stream orders these copies after the upload above has been consumed
-    HIPCHK(hipMemcpyAsync(pin, B->d_scratch + PF_COUNTER_OFF / 4, cbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin, B->counter_lines(), cbytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(pin + cbytes, d_state, ns * sizeof(pf_climb_set), hipMemcpyDeviceToHost, st));
     if (n_wvars)
         HIPCHK(hipMemcpyAsync(pin + cbytes + ns * sizeof(pf_climb_set), d_par[rounds & 1u], n_wvars * 32,
                               hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const unsigned long long* hs = reinterpret_cast<const unsigned long long*>(pin);
     const pf_climb_set* hst = reinterpret_cast<const pf_climb_set*>(pin + cbytes);
     const uint32_t* hv = reinterpret_cast<const uint32_t*>(pin + cbytes + ns * sizeof(pf_climb_set));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
-        for (int k = 0; k < 4; k++) h[k] += hs[i * 16 + k];
     uint64_t n_sat = 0;
     size_t off = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1218,16 +1184,7 @@ int pf_climb_batch_scored(uint64_t handle, uint64_t global_seed, uint32_t rounds
         if (values_out && nv) memcpy(values_out + off * 8, hv + (size_t)wvoff[s] * 8, nv * 32);
         off += nv;
     }
-    if (stats) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
-        stats->evals_full = h[0];
-        stats->cands_decided = h[1];
-        stats->n_sat = n_sat;
-        stats->kernel_ms = ms;
-        stats->timed_out = h[3] ? 1u : 0u;
-    }
-    return 0;
+    return stats ? fill_stats(B, reinterpret_cast<const unsigned long long*>(pin), kSideStats, n_sat, stats) : 0;
 }
 
 int pf_batch_site_counts(uint64_t handle, const uint32_t* set_ids, size_t n, uint32_t* counts_out) {
@@ -1251,23 +1208,17 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
     Batch* B = as_batch(handle);
     if (!B) return fail("pf_census_batch: null batch");
     if (budget == 0) return fail("pf_census_batch: budget must be at least 1");
-    if (n && !set_ids) return fail("pf_census_batch: null set_ids");
     const size_t ns = B->n_sets;
-    {
-        std::vector<uint8_t> seen(ns, 0);
-        for (size_t i = 0; i < n; i++) {
-            if (set_ids[i] >= ns) return fail("pf_census_batch: set %u out of range (%zu sets)", set_ids[i], ns);
-            if (seen[set_ids[i]]) return fail("pf_census_batch: set %u requested twice", set_ids[i]);
-            if (B->h_sites[set_ids[i]] > PF_CENSUS_MAX_SITES)
-                return fail("pf_census_batch: set %u has %u sites (at most %u)", set_ids[i], B->h_sites[set_ids[i]],
-                            PF_CENSUS_MAX_SITES);
-            seen[set_ids[i]] = 1;
-        }
-    }
+    const auto few_sites = [&](uint32_t s) {
+        return B->h_sites[s] > PF_CENSUS_MAX_SITES
+                   ? errorf("pf_census_batch: set %u has %u sites (at most %u)", s, B->h_sites[s], PF_CENSUS_MAX_SITES)
+                   : std::string();
+    };
+    if (failed(check_request("pf_census_batch", ns, set_ids, n, few_sites))) return -1;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0) return 0;
-    const uint32_t groups = (uint32_t)(((uint64_t)budget + 63u) / 64u);
-    if ((uint64_t)n * groups > 0xffffffffull) return fail("pf_census_batch: %zu sets x %u groups is too many items", n, groups);
+    const uint32_t groups = groups_of(budget);
+    if (failed(check_items("pf_census_batch", n, groups))) return -1;
     Dev* D = use_dev(B->device);
     if (!D) return -1;
     hipStream_t st = D->stream;
@@ -1282,14 +1233,10 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
         n_rows += 3ull * B->h_sites[s];
     }
     if (n_rows + ns > 0xffffffffull) return fail("pf_census_batch: %llu row entries", (unsigned long long)n_rows);
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t o_st = 0, o_rows = o_st + al(ns * sizeof(pf_census_set)), o_tab = o_rows + al((size_t)n_rows * 4 + 4),
                  total = o_tab + al(3 * ns * 4);
-    if (!B->s_mem) {
-        B->s_mem = pool_acquire(D, total, &B->s_cap);
-        if (!B->s_mem) return fail("pf_census_batch: hipMalloc(%zu) failed", total);
-    }
-    uint8_t* sb = static_cast<uint8_t*>(B->s_mem);
+    if (ensure(D, B, kCensus, total, "pf_census_batch")) return -1;
+    uint8_t* sb = static_cast<uint8_t*>(B->side[kCensus].mem);
     pf_census_set* d_state = reinterpret_cast<pf_census_set*>(sb + o_st);
     uint32_t* d_rows = reinterpret_cast<uint32_t*>(sb + o_rows);
     uint32_t* d_rowoff = reinterpret_cast<uint32_t*>(sb + o_tab);
@@ -1297,13 +1244,9 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
 
     // this call's sets in launch order: the 8-register ones, then the 16-register ones
     std::vector<uint32_t> req;
-    req.reserve(n);
-    for (int part = 0; part < 2; ++part)
-        for (size_t i = 0; i < n; i++)
-            if ((int)B->h_wide[set_ids[i]] == part) req.push_back(set_ids[i]);
-    const size_t n_narrow = (size_t)std::count_if(req.begin(), req.end(), [&](uint32_t s) { return !B->h_wide[s]; });
+    const size_t n_narrow = request_order(B->h_wide, set_ids, n, req);
 
-    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
+    constexpr size_t cbytes = kCounterBytes;
     const size_t in_bytes = 3 * ns * 4, out_bytes = cbytes + ns * sizeof(pf_census_set) + (size_t)n_rows * 4;
     uint8_t* pin = pinned_staging(std::max(in_bytes, out_bytes));
     if (!pin) return fail("pf_census_batch: no pinned staging of %zu bytes", std::max(in_bytes, out_bytes));
@@ -1313,15 +1256,9 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
     memcpy(pin + 2 * ns * 4, req.data(), n * 4);
     HIPCHK(hipMemcpyAsync(d_rowoff, pin, in_bytes, hipMemcpyHostToDevice, st));
 
-    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
-    uint64_t* d_t0 = reinterpret_cast<uint64_t*>(B->d_scratch + 8);
-    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
     // the launches, back to back on the stream: the scratch reset (found[] is left alone), the
     // census block's reset, the two parts' census launches; nothing here waits for the device
-    hipLaunchKernelGGL(pf_reset_kernel, dim3((PF_SCRATCH_BYTES / 4 + 255u) / 256u), dim3(256), 0, st, B->d_scratch,
-                       (uint32_t)(PF_SCRATCH_BYTES / 4), B->d_found, 0u);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(B->ev0, st));
+    if (reset_scratch(B, st, B->d_found, 0u)) return -1;  // found[] is left alone
     {
         const uint64_t cells = n_rows + ns;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((cells + 255u) / 256u, 1024u);
@@ -1333,30 +1270,24 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
     for (int part = 0; part < 2; ++part) {
         const size_t first = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
         if (np == 0) continue;
-        const uint64_t items = (uint64_t)np * groups;
-        const uint64_t waves = std::min<uint64_t>(items, (uint64_t)D->num_cus * g_waves_per_cu_early);
-        const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
-        hipLaunchKernelGGL(part == 0 ? pf_census_kernel : pf_census_r16_kernel, dim3(blocks),
+        const Grid g = group_grid(g_knobs, D->num_cus, np, groups);
+        hipLaunchKernelGGL(part == 0 ? pf_census_kernel : pf_census_r16_kernel, dim3(g.blocks),
                            dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, d_req + first, (uint32_t)np, B->d_code,
-                           B->d_consts, B->d_schema, B->d_parents, global_seed, budget, groups, deadline, d_t0,
-                           d_state, d_rows, d_counters, d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+                           B->d_consts, B->d_schema, B->d_parents, global_seed, budget, groups, deadline, B->t0(),
+                           d_state, d_rows, B->counters(), B->queue(0, part));
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(B->ev1, st));
     // counters, states and rows in the staging buffer; the stream orders these copies after the
     // upload above has been consumed
-    HIPCHK(hipMemcpyAsync(pin, B->d_scratch + PF_COUNTER_OFF / 4, cbytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pin, B->counter_lines(), cbytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(pin + cbytes, d_state, ns * sizeof(pf_census_set), hipMemcpyDeviceToHost, st));
     if (n_rows)
         HIPCHK(hipMemcpyAsync(pin + cbytes + ns * sizeof(pf_census_set), d_rows, (size_t)n_rows * 4,
                               hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const unsigned long long* hs = reinterpret_cast<const unsigned long long*>(pin);
     const pf_census_set* hst = reinterpret_cast<const pf_census_set*>(pin + cbytes);
     const uint32_t* hr = reinterpret_cast<const uint32_t*>(pin + cbytes + ns * sizeof(pf_census_set));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
-        for (int k = 0; k < 4; k++) h[k] += hs[i * 16 + k];
     uint64_t n_sat = 0;
     size_t off = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1378,16 +1309,7 @@ int pf_census_batch(uint64_t handle, uint64_t global_seed, uint32_t budget, uint
         if (status_out) status_out[i] = is_cut ? PF_CENSUS_CUT : PF_CENSUS_DONE;
         n_sat += bf == 0u;
     }
-    if (stats) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
-        stats->evals_full = h[0];
-        stats->cands_decided = h[1];
-        stats->n_sat = n_sat;
-        stats->kernel_ms = ms;
-        stats->timed_out = h[3] ? 1u : 0u;
-    }
-    return 0;
+    return stats ? fill_stats(B, reinterpret_cast<const unsigned long long*>(pin), kSideStats, n_sat, stats) : 0;
 }
 
 static int eval_launch(Batch* B, uint32_t set, const uint32_t* d_soa, uint32_t n_cand,
@@ -1416,33 +1338,15 @@ int pf_eval_assignments(uint64_t handle, uint32_t set, const uint32_t* soa, uint
     // one pooled block [assignments | verdicts] and the pinned staging buffer for both
     // copies (the GPU-resident ModelCache calls this once per quick-sat query: no hipMalloc /
     // hipFree, no pageable copies — pf_materialize's pattern)
-    const size_t o_out = (bytes + 255) & ~size_t(255), total = o_out + n_cand;
-    size_t cap = 0;
-    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, total, &cap));
+    const size_t o_out = al(bytes), total = o_out + n_cand;
+    Pooled blk(D, total);
+    uint8_t* dm = blk.p;
     if (!dm) return fail("pf_eval_assignments: hipMalloc(%zu) failed", total);
-    uint32_t* d_soa = reinterpret_cast<uint32_t*>(dm);
-    uint8_t* d_out = dm + o_out;
     uint8_t* pin = pinned_staging(std::max<size_t>(bytes, n_cand));
-    int rc = 0;
-    if (pin) memcpy(pin, soa, bytes);
-    if (hipMemcpyAsync(d_soa, pin ? static_cast<const void*>(pin) : static_cast<const void*>(soa), bytes,
-                       hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = -1;
-    if (!rc && eval_launch(B, set, d_soa, n_cand, d_out, st)) rc = -1;
-    // the staging buffer is reused for the verdicts: the stream orders the copy after the
-    // kernel, which ran after the copy-in
-    if (!rc && (hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(sat_out), d_out, n_cand,
-                               hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess))
-        rc = -1;
-    if (!rc && pin) memcpy(sat_out, pin, n_cand);
-    if (rc) {
-        // work may still be in flight on the block: freed after a full synchronisation, never
-        // pooled (the pf_materialize rule)
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
-        return fail("pf_eval_assignments: HIP call failed");
-    }
-    pool_release(D, dm, cap);
+    HIPTRY("pf_eval_assignments", copy_in(dm, pin, {{0, soa, bytes}}, st));
+    if (eval_launch(B, set, reinterpret_cast<const uint32_t*>(dm), n_cand, dm + o_out, st)) return -1;
+    HIPTRY("pf_eval_assignments", copy_out(sat_out, dm + o_out, n_cand, pin, st));
+    blk.release();
     return 0;
 }
 
@@ -1469,7 +1373,6 @@ static int eval_programs(const char* who, int device, const uint32_t* code, size
         consts = pp.pool.data();
         n_const = pp.pool.size() / 8;
     }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t nv = std::max<size_t>(n_vars, 1), n_dev = code_out.size() / 4, n_out = n_sets * (size_t)n_cand;
     const size_t soa_bytes = nv * 8 * (size_t)n_cand * 4;
     const size_t o_code = 0, o_const = al(n_dev * 16 + 16), o_schema = o_const + al(n_const * 32 + 32),  // + the pad slot
@@ -1485,28 +1388,17 @@ static int eval_programs(const char* who, int device, const uint32_t* code, size
     if (n_vars) memcpy(pin + o_soa, soa, soa_bytes);
     hipStream_t st = D->stream;
     if (switch_stream(D, st)) return -1;
-    size_t cap = 0;
-    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, total, &cap));
+    Pooled blk(D, total);
+    uint8_t* dm = blk.p;
     if (!dm) return fail("%s: hipMalloc(%zu) failed", who, total);
-    int rc = 0;
-    if (hipMemcpyAsync(dm, pin, o_out, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
-    if (!rc) {
-        hipLaunchKernelGGL(pf_eval_soa_sets_kernel, dim3((n_cand + 63) / 64, (unsigned)n_sets), dim3(64), 0, st,
-                           reinterpret_cast<const pf_set_desc*>(dm + o_desc),
-                           reinterpret_cast<const uint4*>(dm + o_code), reinterpret_cast<const uint32_t*>(dm + o_const),
-                           reinterpret_cast<const uint4*>(dm + o_schema),
-                           reinterpret_cast<const uint32_t*>(dm + o_soa), n_cand, dm + o_out);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(pin, dm + o_out, n_out, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            rc = -1;
-    }
-    if (rc) {
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
-        return fail("%s: HIP call failed", who);
-    }
-    memcpy(sat_out, pin, n_out);
-    pool_release(D, dm, cap);
+    HIPTRY(who, hipMemcpyAsync(dm, pin, o_out, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pf_eval_soa_sets_kernel, dim3((n_cand + 63) / 64, (unsigned)n_sets), dim3(64), 0, st,
+                       reinterpret_cast<const pf_set_desc*>(dm + o_desc), reinterpret_cast<const uint4*>(dm + o_code),
+                       reinterpret_cast<const uint32_t*>(dm + o_const), reinterpret_cast<const uint4*>(dm + o_schema),
+                       reinterpret_cast<const uint32_t*>(dm + o_soa), n_cand, dm + o_out);
+    HIPTRY(who, hipGetLastError());
+    HIPTRY(who, copy_out(sat_out, dm + o_out, n_out, pin, st));
+    blk.release();
     return 0;
 }
 
@@ -1546,28 +1438,14 @@ static int stream_check(const char* who, Batch* B, const uint32_t* set_ids, size
                         pf_stats* stats) {
     if (!B) return fail("%s: null batch", who);
     if (flags & ~PF_FLAG_SHORTCIRCUIT) return fail("%s: unknown flags 0x%x (PF_FLAG_SHORTCIRCUIT only)", who, flags);
-    if (n && !set_ids) return fail("%s: null set_ids", who);
-    const size_t ns = B->n_sets;
-    std::vector<uint8_t> seen(ns, 0);
-    bool vars = false;
-    for (size_t i = 0; i < n; i++) {
-        if (set_ids[i] >= ns) return fail("%s: set %u out of range (%zu sets)", who, set_ids[i], ns);
-        if (seen[set_ids[i]]) return fail("%s: set %u requested twice", who, set_ids[i]);
-        seen[set_ids[i]] = 1;
-        vars = vars || B->h_descs[set_ids[i]].n_vars != 0;
-    }
+    if (failed(check_request(who, B->n_sets, set_ids, n))) return -1;
+    const bool vars = std::any_of(set_ids, set_ids + n, [&](uint32_t s) { return B->h_descs[s].n_vars != 0; });
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n == 0 || n_cand == 0) return 0;  // no output has an entry to write
     if (!bits && !first && !count) return fail("%s: every output is null", who);
     if (vars && !soa) return fail("%s: null assignments", who);
-    const uint64_t groups = ((uint64_t)n_cand + 63u) / 64u;
-    if ((uint64_t)n * groups > 0xffffffffull) return fail("%s: %zu sets x %llu groups is too many items", who, n,
-                                                          (unsigned long long)groups);
-    return 1;
+    return failed(check_items(who, n, groups_of(n_cand))) ? -1 : 1;
 }
-
-// work-queue items per wave slot that a stream launch aims for (stream_enqueue)
-constexpr uint64_t kStreamItemsPerWave = 32;
 
 // Enqueue one stream call on st (B's device current, the request checked): the request's tables
 // (uploaded only when they differ from the last call's), the reset, the narrow and the wide
@@ -1575,24 +1453,14 @@ constexpr uint64_t kStreamItemsPerWave = 32;
 static int stream_enqueue(Dev* D, Batch* B, const uint32_t* set_ids, size_t n, const uint32_t* d_soa,
                           uint32_t n_cand, uint32_t flags, uint64_t* d_bits, uint32_t* d_first, uint32_t* d_count,
                           hipStream_t st) {
-    const size_t ns = B->n_sets;
-    if (!B->e_mem) {
-        B->e_mem = pool_acquire(D, std::max<size_t>(2 * ns * 4, 256), &B->e_cap);
-        if (!B->e_mem) return fail("pf_eval_batch: hipMalloc(%zu) failed", 2 * ns * 4);
-    }
+    bool fresh = false;
+    if (ensure(D, B, kStream, std::max<size_t>(2 * B->n_sets * 4, 256), "pf_eval_batch", &fresh)) return -1;
+    if (fresh) B->e_req.clear();
     // this call's sets in launch order — d_order's: the 8-register ones, then the 16-register
     // ones, each part longest first — and each one's place in the request
-    std::vector<uint32_t> place(ns, 0xffffffffu), tab(2 * n);
-    for (size_t i = 0; i < n; i++) place[set_ids[i]] = (uint32_t)i;
-    size_t k = 0, n_narrow = 0;
-    for (uint32_t s : B->h_order) {
-        if (place[s] == 0xffffffffu) continue;
-        tab[k] = s;
-        tab[n + k] = place[s];
-        n_narrow += !B->h_wide[s];
-        k++;
-    }
-    uint32_t* d_req = static_cast<uint32_t*>(B->e_mem);
+    std::vector<uint32_t> tab;
+    const size_t n_narrow = batch_order(B->h_order, B->h_wide, set_ids, n, tab);
+    uint32_t* d_req = static_cast<uint32_t*>(B->side[kStream].mem);
     uint32_t* d_pos = d_req + n;
     if (tab != B->e_req) {
         // a copy from pageable memory: drained before the table goes out of scope.  Only a call
@@ -1602,9 +1470,7 @@ static int stream_enqueue(Dev* D, Batch* B, const uint32_t* set_ids, size_t n, c
         HIPCHK(hipStreamSynchronize(st));
         B->e_req = std::move(tab);
     }
-    const uint32_t groups = (uint32_t)(((uint64_t)n_cand + 63u) / 64u);
-    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(B->d_scratch);
-    uint32_t* d_queue = B->d_scratch + PF_EARLY_QUEUE_OFF / 4;
+    const uint32_t groups = groups_of(n_cand);
     // the caller's first[], or the batch's found[] (n <= n_sets entries): the kernels count the
     // sets with a witness through it
     uint32_t* first = d_first ? d_first : B->d_found;
@@ -1625,47 +1491,15 @@ static int stream_enqueue(Dev* D, Batch* B, const uint32_t* set_ids, size_t n, c
     for (int part = 0; part < 2; ++part) {
         const size_t begin = part ? n_narrow : 0, np = part ? n - n_narrow : n_narrow;
         if (np == 0) continue;
-        // an item is a run of per_item groups of one set: about kStreamItemsPerWave items for every
-        // wave of a chip-filling grid (the claim and the set's descriptor are paid per item, the
-        // last item of a wave is the launch's tail), one group each while the grid is not full
-        const uint64_t slots = (uint64_t)D->num_cus * g_waves_per_cu_early;
-        uint64_t per_item = std::max<uint64_t>(1, (uint64_t)np * groups / (slots * kStreamItemsPerWave));
-        if (chunk_env) per_item = chunk_env;
-        per_item = std::min<uint64_t>(per_item, groups);
-        const uint64_t items = (uint64_t)np * ((groups + per_item - 1) / per_item);
-        const uint64_t waves = std::min<uint64_t>(items, slots);
-        const uint32_t blocks = (uint32_t)((waves + PF_SEARCH_WG_WAVES - 1) / PF_SEARCH_WG_WAVES);
-        hipLaunchKernelGGL(part == 0 ? pf_eval_stream_kernel : pf_eval_stream_r16_kernel, dim3(blocks),
+        const Grid g = stream_grid(g_knobs, D->num_cus, np, groups, chunk_env);
+        hipLaunchKernelGGL(part == 0 ? pf_eval_stream_kernel : pf_eval_stream_r16_kernel, dim3(g.blocks),
                            dim3(64 * PF_SEARCH_WG_WAVES), 0, st, B->d_descs, d_req + begin, d_pos + begin, (uint32_t)np,
-                           B->d_code, B->d_consts, B->d_schema, d_soa, n_cand, groups, (uint32_t)per_item, flags,
-                           reinterpret_cast<unsigned long long*>(d_bits), first, d_count, d_counters,
-                           d_queue + part * PF_EARLY_QUEUES * PF_EARLY_QUEUE_STRIDE);
+                           B->d_code, B->d_consts, B->d_schema, d_soa, n_cand, groups, g.per, flags,
+                           reinterpret_cast<unsigned long long*>(d_bits), first, d_count, B->counters(),
+                           B->queue(0, part));
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(B->ev1, st));
-    return 0;
-}
-
-// Wait for B's stream call on st and read its counters (line slot 4: the sets with a witness).
-static int stream_collect(Batch* B, hipStream_t st, pf_stats* stats) {
-    constexpr size_t cbytes = PF_COUNTER_STRIPES * 128;
-    unsigned long long hs[PF_COUNTER_STRIPES * 16];
-    uint8_t* pin = pinned_staging(cbytes);
-    HIPCHK(hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(hs), B->d_scratch + PF_COUNTER_OFF / 4,
-                          cbytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (pin) memcpy(hs, pin, cbytes);
-    unsigned long long h[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < PF_COUNTER_STRIPES; i++)
-        for (int k = 0; k < 5; k++) h[k] += hs[i * 16 + k];
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, B->ev0, B->ev1));
-    stats->evals_full = h[0];
-    stats->cands_decided = h[1];
-    stats->ops = 0;
-    stats->n_sat = h[4];
-    stats->kernel_ms = ms;
-    stats->timed_out = 0u;
     return 0;
 }
 
@@ -1682,7 +1516,7 @@ int pf_eval_batch_dev(uint64_t handle, const uint32_t* set_ids, size_t n, const 
     hipStream_t st = pick_stream(D, stream);
     if (switch_stream(D, st)) return -1;
     if (stream_enqueue(D, B, set_ids, n, d_soa, n_cand, flags, d_bits, d_first, d_count, st)) return -1;
-    return stats ? stream_collect(B, st, stats) : 0;
+    return stats ? check_collect(B, st, kStreamStats, stats) : 0;
 }
 
 int pf_eval_batch(uint64_t handle, const uint32_t* set_ids, size_t n, const uint32_t* soa, uint32_t n_cand,
@@ -1698,41 +1532,30 @@ int pf_eval_batch(uint64_t handle, const uint32_t* set_ids, size_t n, const uint
     if (switch_stream(D, st)) return -1;
     // one pooled block [assignments | bits | first | count] and the pinned staging buffer for both
     // copies (pf_eval_assignments' pattern)
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t words = ((size_t)n_cand + 63) / 64;
     const size_t soa_bytes = soa ? B->n_vars * 8 * (size_t)n_cand * 4 : 0;
     const size_t o_bits = al(std::max<size_t>(soa_bytes, 4)), o_first = o_bits + al(n * words * 8),
                  o_count = o_first + al(n * 4), total = o_count + al(n * 4), out_bytes = total - o_bits;
-    size_t cap = 0;
-    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, total, &cap));
+    Pooled blk(D, total);
+    uint8_t* dm = blk.p;
     if (!dm) return fail("pf_eval_batch: hipMalloc(%zu) failed", total);
     uint8_t* pin = pinned_staging(std::max(soa_bytes, out_bytes));
-    int rc = pin ? 0 : -1;
-    if (!rc && soa_bytes) {
-        memcpy(pin, soa, soa_bytes);
-        if (hipMemcpyAsync(dm, pin, soa_bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
-    }
-    if (!rc && stream_enqueue(D, B, set_ids, n, reinterpret_cast<const uint32_t*>(dm), n_cand, flags,
-                              bits_out ? reinterpret_cast<uint64_t*>(dm + o_bits) : nullptr,
-                              first_out ? reinterpret_cast<uint32_t*>(dm + o_first) : nullptr,
-                              count_out ? reinterpret_cast<uint32_t*>(dm + o_count) : nullptr, st))
-        rc = -2;
-    // the staging buffer is reused for the results: the stream orders the copy after the kernels,
-    // which ran after the copy-in
-    if (!rc && (hipMemcpyAsync(pin, dm + o_bits, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess))
-        rc = -1;
-    if (rc) {
-        // work may still be in flight on the block: freed after a full synchronisation, never
-        // pooled (the pf_materialize rule)
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
-        return rc == -2 ? -1 : fail("pf_eval_batch: HIP call failed");
-    }
+    if (!pin) return fail("pf_eval_batch: HIP call failed");
+    if (soa_bytes) HIPTRY("pf_eval_batch", copy_in(dm, pin, {{0, soa, soa_bytes}}, st));
+    if (stream_enqueue(D, B, set_ids, n, reinterpret_cast<const uint32_t*>(dm), n_cand, flags,
+                       bits_out ? reinterpret_cast<uint64_t*>(dm + o_bits) : nullptr,
+                       first_out ? reinterpret_cast<uint32_t*>(dm + o_first) : nullptr,
+                       count_out ? reinterpret_cast<uint32_t*>(dm + o_count) : nullptr, st))
+        return -1;
+    // the staging buffer is reused for the results, [bits | first | count] as in the block: the
+    // stream orders the copy after the kernels, which ran after the copy-in
+    HIPTRY("pf_eval_batch", hipMemcpyAsync(pin, dm + o_bits, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPTRY("pf_eval_batch", hipStreamSynchronize(st));
     if (bits_out) memcpy(bits_out, pin, n * words * 8);
     if (first_out) memcpy(first_out, pin + (o_first - o_bits), n * 4);
     if (count_out) memcpy(count_out, pin + (o_count - o_bits), n * 4);
-    pool_release(D, dm, cap);
-    return stats ? stream_collect(B, st, stats) : 0;
+    blk.release();
+    return stats ? check_collect(B, st, kStreamStats, stats) : 0;
 }
 
 int pf_keccak256_batch(const uint8_t* data, const uint64_t* offsets, size_t n, uint8_t* out32) {
@@ -1748,37 +1571,18 @@ int pf_keccak256_batch(const uint8_t* data, const uint64_t* offsets, size_t n, u
     // one pooled block [offsets | messages | digests] and one copy each way through the
     // pinned staging buffer (a concretisation call hashes a handful of preimages: three
     // hipMalloc / hipFree pairs and pageable copies were most of its latency)
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t o_off = 0, o_data = al((n + 1) * 8), o_out = o_data + al(total ? total : 8),
                  all = o_out + n * 32;
-    size_t cap = 0;
-    uint8_t* dm = static_cast<uint8_t*>(pool_acquire(D, all, &cap));
+    Pooled blk(D, all);
+    uint8_t* dm = blk.p;
     if (!dm) return fail("pf_keccak256_batch: hipMalloc(%zu) failed", all);
     uint8_t* pin = pinned_staging(std::max<size_t>(o_out, n * 32));
-    int rc = 0;
-    if (pin) {
-        memcpy(pin + o_off, offsets, (n + 1) * 8);
-        if (total) memcpy(pin + o_data, data, total);
-        if (hipMemcpyAsync(dm, pin, o_data + total, hipMemcpyHostToDevice, st) != hipSuccess) rc = -1;
-    } else if (hipMemcpyAsync(dm + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-               (total && hipMemcpyAsync(dm + o_data, data, total, hipMemcpyHostToDevice, st) != hipSuccess)) {
-        rc = -1;
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(pf_keccak_var_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
-                           dm + o_data, reinterpret_cast<const uint64_t*>(dm + o_off), (uint64_t)n, dm + o_out);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(pin ? static_cast<void*>(pin) : static_cast<void*>(out32), dm + o_out, n * 32,
-                           hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            rc = -1;
-    }
-    if (rc) {
-        if (hipDeviceSynchronize() == hipSuccess) hipFree(dm);
-        return fail("pf_keccak256_batch: HIP call failed");
-    }
-    if (pin) memcpy(out32, pin, n * 32);
-    pool_release(D, dm, cap);
+    HIPTRY("pf_keccak256_batch", copy_in(dm, pin, {{o_off, offsets, (n + 1) * 8}, {o_data, data, total}}, st));
+    hipLaunchKernelGGL(pf_keccak_var_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, dm + o_data,
+                       reinterpret_cast<const uint64_t*>(dm + o_off), (uint64_t)n, dm + o_out);
+    HIPTRY("pf_keccak256_batch", hipGetLastError());
+    HIPTRY("pf_keccak256_batch", copy_out(out32, dm + o_out, n * 32, pin, st));
+    blk.release();
     return 0;
 }
 
